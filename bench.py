@@ -9,13 +9,19 @@ the timed step: one copy of image + target).  N > 1: one process per GPU (torch.
 (3-float all-reduce) + one flat-gradient RCCL all-reduce per step; per-GPU batch fixed (weak
 scaling); time = max over ranks.
 
-Also reported: eval forward ms/patch (bs 1 and 4), config 5 (32->256, 64^3, step-based mixed
-domains) data-parallel over the job's GPUs, the grouped-conv variant on one GPU, the config-4
-whole-volume sliding-window
+A plain run (`bench.py --gpus N --steps K --warmup W`) sets up, warms up, times the K steps and
+prints the result line (metric, value, unit, ms_per_step, ...).  `--dump-outputs DIR` also
+writes what the last timed step gave its caller (loss, updated flat parameters, flat gradient)
+as DIR/<name>.npy; the inputs are seeded, so two builds can be compared output for output.
+
+With `--full` also reported: eval forward ms/patch (bs 1 and 4), config 5 (32->256, 64^3,
+step-based mixed domains) data-parallel over the job's GPUs, the grouped-conv variant on one GPU,
+the config-4 whole-volume sliding-window
 inference of a 256^3 synthetic PET volume (seconds, ms/window; light_unet.utils), the roofline of
 the dominant kernel measured with HIP events around back-to-back replays of its C-ABI call, and
 the CPU baseline (the torch-CPU oracle restatement of the same network on this host's cores,
-rank 0 only, bounded sample).
+rank 0 only, bounded sample).  The `--no-*` options drop single legs of a `--full` run.  The
+headline step is the same with and without `--full`.
 """
 import argparse
 import json
@@ -66,10 +72,21 @@ def parse():
     ap.add_argument("--dist-backend", default="nccl", choices=["nccl", "gloo"])
     ap.add_argument("--one-device", action="store_true")
     ap.add_argument("--dump-calls", default=None,
-                    help="write the recorded step's C-ABI calls (name, family, label, algorithmic "
+                    help="(with --full) write the recorded step's C-ABI calls (name, family, label, algorithmic "
                          "bytes) in launch order to this JSON file (tools/instep.py aligns them "
                          "with a rocprofv3 kernel trace of the graph-replayed step)")
+    ap.add_argument("--full", action="store_true",
+                    help="also run every side leg (eval forward, sliding window, config 5, grouped, "
+                         "bf16, drop-in, data path, exchange probe, rooflines, CPU baseline); a "
+                         "plain run times the headline step only")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed steps write what the last one gave its caller (loss, "
+                         "params, grads) as DIR/<name>.npy (float32)")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
+    if args.dump_calls and not args.full:
+        ap.error("--dump-calls records the roofline leg's step: add --full")
     if args.gpus is None:
         args.gpus = int(os.environ.get("WORLD_SIZE", "1"))
     return args
@@ -85,6 +102,23 @@ def synthetic_pool(n_pool, bs, size, rank, device):
         t = (rng.random((bs, 1, size, size, size)) > 0.97).astype(np.float32)
         pool.append(torch.from_numpy(np.stack([x, t])).to(device))
     return pool
+
+
+DUMP_BUDGET = 64 * 2 ** 20   # bytes, over all arrays of one --dump-outputs
+
+
+def dump_outputs(dirname, arrays):
+    """Write {name: device tensor} as dirname/<name>.npy (float32).  An array is written whole
+    while it fits an equal share of DUMP_BUDGET, a larger one as a fixed sample (seed 0) of its
+    flattened elements: the same indices in every run."""
+    os.makedirs(dirname, exist_ok=True)
+    share = DUMP_BUDGET // (4 * len(arrays))   # elements per array
+    for name, t in arrays.items():
+        a = t.detach().float().cpu().numpy()
+        if a.size > share:
+            idx = np.sort(np.random.default_rng(0).choice(a.size, share, replace=False))
+            a = a.reshape(-1)[idx]
+        np.save(os.path.join(dirname, name + ".npy"), a)
 
 
 def dw_bytes(N, C, S, e=4, acc=0):
@@ -990,30 +1024,34 @@ def main():
     xt_static = pool[0].clone()
     x_static, t_static = xt_static[0], xt_static[1]
 
-    # roofline leg (eager, instrumented): every C-ABI call of one step recorded at its real shapes
-    # and buffers; the dominant call and the depthwise / GEMM families re-timed from the record
-    N, S = args.batch, args.size ** 3
-    cdom = 2 * enc[0]      # up3.res_block conv1.depthwise: [N, 2*c0, D^3] backward
-    dom_name = "l3u_dw3_bwd" + ("_bf16" if args.dtype == "bf16" else "")
+    # three eager steps come before the capture in every run, so the timed steps start from the
+    # same parameters, AdamW state and Dropout3d counter with and without --full
     for i in range(2):
         step(xs[i % 8], ts[i % 8])
     torch.cuda.synchronize()
-    rec = StepRecorder()
-    restore = rec.wrap(nat, model.engine)
+    if args.full:
+        # roofline leg (instrumented): every C-ABI call of the third step recorded at its real
+        # shapes and buffers; the dominant call and the depthwise / GEMM families re-timed from
+        # the record
+        rec = StepRecorder()
+        restore = rec.wrap(nat, model.engine)
     step(xs[2], ts[2])
     torch.cuda.synchronize()
-    restore()
-    seg_items_from(model.engine)
-    orig = rec.orig
-    dom_calls = [(n, a) for n, a in rec.calls if n == dom_name and a[-5] == cdom and a[-4] == args.size]
-    dom_ms = StepRecorder.time_calls(orig, dom_calls[:1], reps=50)[0] if dom_calls else None
-    fams = family_rooflines(orig, rec.calls) if rank == 0 else None
-    n_launch_calls = len(rec.calls)
-    if args.dump_calls and rank == 0:
-        with open(args.dump_calls, "w") as f:
-            json.dump([dict(zip(("name", "family", "label", "bytes"),
-                                (n,) + (call_bytes(n, a) or (None, None, None)))) for n, a in rec.calls], f)
-    rec = None   # releases the recorded step's buffers
+    if args.full:
+        restore()
+        seg_items_from(model.engine)
+        orig = rec.orig
+        cdom = 2 * enc[0]      # up3.res_block conv1.depthwise: [N, 2*c0, D^3] backward
+        dom_name = "l3u_dw3_bwd" + ("_bf16" if args.dtype == "bf16" else "")
+        dom_calls = [(n, a) for n, a in rec.calls if n == dom_name and a[-5] == cdom and a[-4] == args.size]
+        dom_ms = StepRecorder.time_calls(orig, dom_calls[:1], reps=50)[0] if dom_calls else None
+        fams = family_rooflines(orig, rec.calls) if rank == 0 else None
+        n_launch_calls = len(rec.calls)
+        if args.dump_calls and rank == 0:
+            with open(args.dump_calls, "w") as f:
+                json.dump([dict(zip(("name", "family", "label", "bytes"),
+                                    (n,) + (call_bytes(n, a) or (None, None, None)))) for n, a in rec.calls], f)
+        rec = None   # releases the recorded step's buffers
 
     if args.no_graph:
         def run(i):
@@ -1046,32 +1084,16 @@ def main():
     final_loss = float(loss.item())
     if not np.isfinite(final_loss):
         raise SystemExit(f"non-finite loss {final_loss}")
+    if args.dump_outputs and rank == 0:
+        # what the step hands its caller: the returned loss and, in place, the updated flat
+        # parameters and the flat gradient of the last batch
+        dump_outputs(args.dump_outputs, {"loss": loss, "params": step.flat, "grads": step.gflat})
 
-    sliding = sliding_bench(model, device) if (rank == 0 and not args.no_sliding) else None
-    cfg5 = config5_bench(device, world, rank) if not args.no_config5 else None   # every rank
-    if cfg5 is not None:
-        cfg5["roofline_in_step"] = instep_evidence("c5", None)
-        cfg5["step_traffic"] = step_traffic_evidence("c5", cfg5.get("ms_per_step"))
-    cfg5 = cfg5 if rank == 0 else None
-    grouped = grouped_bench(device) if (rank == 0 and not args.no_grouped) else None
-    bf16 = bf16_bench(device, args, enc, world, rank, pool) if (args.dtype == "fp32" and not args.no_bf16) else None
-    dropin = dropin_bench(device) if (rank == 0 and not args.no_dropin) else None
-    lesion_r = lesion_bench(device) if (rank == 0 and not args.no_data) else None
-    patches_r = patches_bench(device) if (rank == 0 and not args.no_data) else None
-    exch = exchange_probe() if (world == 1 and not args.no_exchange) else None
-    fwd1 = fwd_ms_per_patch(model, 1, args.size, device) if rank == 0 else None
-    fwd4 = fwd_ms_per_patch(model, args.batch, args.size, device) if rank == 0 else None
     out = None
     if rank == 0:
-        patches = world * args.batch * args.steps
-        value = patches / elapsed
-        dacc = int(bool(dom_calls[0][1][8])) if dom_calls else 0   # accumulates into d(input)
-        dbytes = dw_bytes(N, cdom, S, e=2 if args.dtype == "bf16" else 4, acc=dacc)
-        achieved = dbytes / (dom_ms * 1e-3) / 1e9 if dom_ms else None
-        traffic, traffic_src, traffic_tree = pmc_traffic(N, cdom, args.size, dacc)
         out = {
             "metric": METRIC,
-            "value": round(value, 2),
+            "value": round(world * args.batch * args.steps / elapsed, 2),
             "unit": "patches/s",
             "n_gpus": world,
             "steps": args.steps,
@@ -1092,49 +1114,85 @@ def main():
                                         else "eager between graph segments") if step.exchange
                                        else None),
                        "graph": not args.no_graph},
-            "fwd_ms_per_patch": {"bs1": round(fwd1, 4), f"bs{args.batch}": round(fwd4, 4)},
             "final_loss": round(final_loss, 6),
-            "sliding_window_256": sliding,
-            "config5": cfg5,
-            "grouped_1gpu": grouped,
-            "bf16": bf16,
-            "dropin": dropin,
-            "lesion_256": lesion_r,
-            "patches": patches_r,
-            "launches_per_step": n_launch_calls,
-            "exchange": exch,
-            "roofline": {
-                "kernel": f"l3u_dw3_bwd [{N},{cdom},{args.size}^3] (up3.res_block.conv1.depthwise "
-                          "backward: one single-pass launch, data and weight gradients from one "
-                          "LDS-DMA-staged read of dZ and A"
-                          + (", adding to the shortcut's d(input))" if dacc else ")"),
-                "bound": "hbm",
-                "achieved": round(achieved, 1) if achieved else None,
-                "peak": HBM_PEAK_GBS,
-                "unit": "GB/s",
-                "frac": round(achieved / HBM_PEAK_GBS, 4) if achieved else None,
-                "traffic": traffic,
-                "traffic_source": traffic_src,
-                "traffic_tree_matches": traffic_tree,
-                "algorithmic_bytes": dbytes,
-                "avg_launch_ms": round(dom_ms, 5) if dom_ms else None,
-                "cache_exceeding": dw_bwd_cache_exceeding(device),
-                "in_step": instep_evidence(
-                    "c5" if enc == (32, 64, 128, 256) and args.size == 64 else args.dtype, n_launch_calls),
-                "depthwise": fams["dw"],
-                "gemm": dict(fams["gemm"], calls=sorted(fams["gemm"]["calls"], key=lambda r: -r["us"])[:5],
-                             mfma=gemm_mfma_evidence()),
-                # the InstanceNorm / block-tail launches and the out_conv + loss launches
-                "norm": dict(fams["norm"], calls=sorted(fams["norm"]["calls"], key=lambda r: -r["us"])[:5]),
-                "io": fams["io"],
-            },
         }
-        if world == 1 and not args.no_cpu_baseline:
-            out["cpu_baseline"] = cpu_baseline(args, enc)
+    if args.full:
+        side = side_legs(args, enc, model, pool, device, world, rank,
+                         dom_calls, dom_ms, fams, n_launch_calls)
+        if rank == 0:
+            out.update(side)
+    if rank == 0:
         print(json.dumps(out), flush=True)
     if world > 1:
         dist.barrier()
         dist.destroy_process_group()
+    return out
+
+
+def side_legs(args, enc, model, pool, device, world, rank, dom_calls, dom_ms, fams, n_launch_calls):
+    """Everything a --full run reports beside the headline step (after it; the `--no-*` options
+    drop single legs).  Every rank runs the data-parallel legs; the result keys on rank 0, else
+    None."""
+    N, S, cdom = args.batch, args.size ** 3, 2 * enc[0]
+    sliding = sliding_bench(model, device) if (rank == 0 and not args.no_sliding) else None
+    cfg5 = config5_bench(device, world, rank) if not args.no_config5 else None   # every rank
+    if cfg5 is not None:
+        cfg5["roofline_in_step"] = instep_evidence("c5", None)
+        cfg5["step_traffic"] = step_traffic_evidence("c5", cfg5.get("ms_per_step"))
+    cfg5 = cfg5 if rank == 0 else None
+    grouped = grouped_bench(device) if (rank == 0 and not args.no_grouped) else None
+    bf16 = bf16_bench(device, args, enc, world, rank, pool) if (args.dtype == "fp32" and not args.no_bf16) else None
+    dropin = dropin_bench(device) if (rank == 0 and not args.no_dropin) else None
+    lesion_r = lesion_bench(device) if (rank == 0 and not args.no_data) else None
+    patches_r = patches_bench(device) if (rank == 0 and not args.no_data) else None
+    exch = exchange_probe() if (world == 1 and not args.no_exchange) else None
+    fwd1 = fwd_ms_per_patch(model, 1, args.size, device) if rank == 0 else None
+    fwd4 = fwd_ms_per_patch(model, args.batch, args.size, device) if rank == 0 else None
+    if rank != 0:
+        return None
+    dacc = int(bool(dom_calls[0][1][8])) if dom_calls else 0   # accumulates into d(input)
+    dbytes = dw_bytes(N, cdom, S, e=2 if args.dtype == "bf16" else 4, acc=dacc)
+    achieved = dbytes / (dom_ms * 1e-3) / 1e9 if dom_ms else None
+    traffic, traffic_src, traffic_tree = pmc_traffic(N, cdom, args.size, dacc)
+    out = {
+        "fwd_ms_per_patch": {"bs1": round(fwd1, 4), f"bs{args.batch}": round(fwd4, 4)},
+        "sliding_window_256": sliding,
+        "config5": cfg5,
+        "grouped_1gpu": grouped,
+        "bf16": bf16,
+        "dropin": dropin,
+        "lesion_256": lesion_r,
+        "patches": patches_r,
+        "launches_per_step": n_launch_calls,
+        "exchange": exch,
+        "roofline": {
+            "kernel": f"l3u_dw3_bwd [{N},{cdom},{args.size}^3] (up3.res_block.conv1.depthwise "
+                      "backward: one single-pass launch, data and weight gradients from one "
+                      "LDS-DMA-staged read of dZ and A"
+                      + (", adding to the shortcut's d(input))" if dacc else ")"),
+            "bound": "hbm",
+            "achieved": round(achieved, 1) if achieved else None,
+            "peak": HBM_PEAK_GBS,
+            "unit": "GB/s",
+            "frac": round(achieved / HBM_PEAK_GBS, 4) if achieved else None,
+            "traffic": traffic,
+            "traffic_source": traffic_src,
+            "traffic_tree_matches": traffic_tree,
+            "algorithmic_bytes": dbytes,
+            "avg_launch_ms": round(dom_ms, 5) if dom_ms else None,
+            "cache_exceeding": dw_bwd_cache_exceeding(device),
+            "in_step": instep_evidence(
+                "c5" if enc == (32, 64, 128, 256) and args.size == 64 else args.dtype, n_launch_calls),
+            "depthwise": fams["dw"],
+            "gemm": dict(fams["gemm"], calls=sorted(fams["gemm"]["calls"], key=lambda r: -r["us"])[:5],
+                         mfma=gemm_mfma_evidence()),
+            # the InstanceNorm / block-tail launches and the out_conv + loss launches
+            "norm": dict(fams["norm"], calls=sorted(fams["norm"]["calls"], key=lambda r: -r["us"])[:5]),
+            "io": fams["io"],
+        },
+    }
+    if world == 1 and not args.no_cpu_baseline:
+        out["cpu_baseline"] = cpu_baseline(args, enc)
     return out
 
 

@@ -56,6 +56,76 @@ def test_bench_self_launches_two_ranks(cuda):
     assert out["value"] > 0 and out["final_loss"] == out["final_loss"]
 
 
+SIDE_KEYS = ("fwd_ms_per_patch", "sliding_window_256", "config5", "grouped_1gpu", "bf16", "dropin",
+             "lesion_256", "patches", "launches_per_step", "exchange", "roofline", "cpu_baseline")
+
+
+@pytest.mark.gpu
+def test_plain_run_times_the_headline_only_and_dumps_outputs(cuda, tmp_path, monkeypatch, capsys):
+    """GPU: a plain `bench.py --gpus 1 --steps 3 --warmup 1 --dump-outputs DIR` (in this process)
+    prints the headline keys without the --full legs and writes the last step's loss, flat
+    parameters and flat gradient as float32 .npy."""
+    import numpy as np
+    sys.path.insert(0, ROOT)
+    import bench
+    for k in ("WORLD_SIZE", "RANK", "LOCAL_RANK"):
+        monkeypatch.delenv(k, raising=False)
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--gpus", "1", "--steps", "3", "--warmup", "1",
+                                      "--dump-outputs", str(tmp_path / "o")])
+    out = bench.main()
+    lines = [ln for ln in capsys.readouterr().out.splitlines() if ln.startswith("{")]
+    assert len(lines) == 1 and json.loads(lines[0]) == out
+    assert out["metric"] == bench.METRIC and out["unit"] == "patches/s" and out["dtype"] == "fp32"
+    assert out["higher_is_better"] is True and out["steps"] == 3 and out["warmup"] == 1
+    assert out["ms_per_step"] > 0
+    assert abs(out["value"] * out["ms_per_step"] / (1000 * 4) - 1) < 1e-3   # bs 4 patches per step
+    assert not set(SIDE_KEYS) & set(out)
+    got = {f: np.load(tmp_path / "o" / f) for f in sorted(os.listdir(tmp_path / "o"))}
+    assert sorted(got) == ["grads.npy", "loss.npy", "params.npy"]
+    assert all(a.dtype == np.float32 and np.isfinite(a).all() for a in got.values())
+    assert got["loss.npy"].shape == () and abs(float(got["loss.npy"]) - out["final_loss"]) <= 1e-6
+    assert got["params.npy"].shape == got["grads.npy"].shape == (217228,)   # the 16->128 model
+    assert np.abs(got["grads.npy"]).max() > 0
+
+
+def test_dump_outputs_samples_large_arrays(tmp_path, monkeypatch):
+    """CPU: dump_outputs writes float32 .npy; an array over its share of the byte budget becomes a
+    fixed sample of its elements (the same indices in every call), a smaller one is whole."""
+    import numpy as np
+    import torch
+    sys.path.insert(0, ROOT)
+    import bench
+    monkeypatch.setattr(bench, "DUMP_BUDGET", 2 * 4 * 100)   # 100 elements per array
+    big = torch.arange(1000, dtype=torch.float64).reshape(10, 100)
+    small = torch.arange(6, dtype=torch.bfloat16).reshape(2, 3)
+    for d in ("a", "b"):
+        bench.dump_outputs(str(tmp_path / d), {"big": big, "small": small})
+    a, b = np.load(tmp_path / "a" / "big.npy"), np.load(tmp_path / "b" / "big.npy")
+    assert a.dtype == np.float32 and a.shape == (100,) and np.array_equal(a, b)
+    assert np.all(np.diff(a) > 0) and a.max() < 1000   # distinct elements of `big`, in order
+    s = np.load(tmp_path / "a" / "small.npy")
+    assert s.dtype == np.float32 and s.shape == (2, 3) and np.array_equal(s.ravel(), np.arange(6))
+
+
+def test_bench_options(monkeypatch, capsys):
+    """CPU: --full and --dump-outputs parse; --dump-calls without --full and --steps 0 are
+    usage errors."""
+    sys.path.insert(0, ROOT)
+    import bench
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--gpus", "1", "--steps", "5", "--warmup", "2"])
+    a = bench.parse()
+    assert (a.full, a.dump_outputs, a.steps, a.warmup) == (False, None, 5, 2)
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--full", "--dump-outputs", "d", "--dump-calls", "c.json"])
+    a = bench.parse()
+    assert a.full and a.dump_outputs == "d" and a.dump_calls == "c.json"
+    for bad in (["--dump-calls", "c.json"], ["--steps", "0"]):
+        monkeypatch.setattr(sys, "argv", ["bench.py"] + bad)
+        with pytest.raises(SystemExit) as e:
+            bench.parse()
+        assert e.value.code == 2
+    capsys.readouterr()
+
+
 def test_paired_call_bytes_are_the_two_calls():
     """CPU: the in-step byte model of a paired GEMM backward launch (l3u_pw_bwd2,
     l3u_pw_bwd_tail_pair) is the sum of the two calls it replaces, so pairing does not move the

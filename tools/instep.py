@@ -1,7 +1,7 @@
 """In-step rooflines of the depthwise, GEMM, gradient-reduction, InstanceNorm / block-tail ("norm") and
 out_conv + loss ("io") families: the rocprofv3 kernel trace of the
 graph-replayed training step (tools/profile.sh) aligned launch by launch with the C-ABI calls
-of the same step (bench.py --dump-calls: name, family, label, algorithmic bytes).
+of the same step (bench.py --full --dump-calls: name, family, label, algorithmic bytes).
 
 Every kernel's duration is its mean over the complete steps of the trace (steps end at each AdamW
 launch, as tools/steplist.py); kernels that are not C-ABI launches (the runtime's batch copy) are
