@@ -191,6 +191,7 @@ int l3u_pw_bwd(const float* dy, long long dy_nstride, const float* y, long long 
 /* the block tail's two pointwise backwards (conv2.pointwise: sel 1, yr = y2; the Conv1x1
  * shortcut: sel 2, yr = r) of l3u_pw_bwd_tail in ONE launch, dout as l3u_pw_bwd_tail (dscale and
  * dpool NULL), l3u_pw_bwd_tail_r1 (dscale) or l3u_pw_bwd_tail_up (dpool, idx and the plane Hf x Wf);
+ * dscale and dpool are mutually exclusive (both given: hipErrorInvalidValue, nothing launched);
  * a rank-1 yr (negative yrb_nstride, fp32) only for the second problem and only when J, Ka, Kb
  * <= 16; each problem's partials as l3u_pw_bwd_nparts(N, J, K, S), results bit-identical to the
  * two calls.                                                                                    */

@@ -853,7 +853,9 @@ int outconv_fwd_impl(const T* h, long long h_nstride, const float* w, const floa
                      const float* t, float* ftl_part, int N, int C, int S, hipStream_t stream) {
   L3U_REQUIRE(N > 0 && C > 0 && S > 0);
   L3U_REQUIRE(t == nullptr || ftl_part != nullptr);
-  const bool vec = S % 4 == 0 && h_nstride % 4 == 0 && C <= 32;   // the vector form holds <= 32 channels
+  // the vector form holds <= 32 channels and takes 16-byte loads / stores of t, h and p
+  const bool vec = S % 4 == 0 && h_nstride % 4 == 0 && C <= 32 && ((uintptr_t)p & 15) == 0 &&
+                   ((uintptr_t)t & 15) == 0 && ((uintptr_t)h & (4 * sizeof(T) - 1)) == 0;
   dim3 grid((S + 1023) / 1024, N);
   if (vec) hipLaunchKernelGGL((outconv_fwd_kernel<T, true>), grid, dim3(256), 0, stream, h, h_nstride, w, b, p, t, ftl_part, C, S);
   else hipLaunchKernelGGL((outconv_fwd_kernel<T, false>), grid, dim3(256), 0, stream, h, h_nstride, w, b, p, t, ftl_part, C, S);
@@ -868,7 +870,10 @@ int outconv_bwd_impl(const float* dp, const float* p, const float* t, const doub
                      const float* fpart = nullptr, int fnp = 0, int dz_only = 0) {
   L3U_REQUIRE(N > 0 && C > 0 && C <= 32 && S > 0);
   L3U_REQUIRE(dp != nullptr || (t != nullptr && (sums != nullptr || (fpart != nullptr && fnp > 0))));
-  const bool vec = S % 4 == 0 && h_nstride % 4 == 0 && dh_nstride % 4 == 0;
+  // (the vector form takes 16-byte loads / stores of p, t or dp, h and dh)
+  const bool vec = S % 4 == 0 && h_nstride % 4 == 0 && dh_nstride % 4 == 0 &&
+                   (((uintptr_t)p | (uintptr_t)t | (uintptr_t)dp | (uintptr_t)dh) & 15) == 0 &&
+                   ((uintptr_t)h & (4 * sizeof(T) - 1)) == 0;
   dim3 grid((S + 1023) / 1024, N);
   const size_t lds = 4 * (C + 1) * sizeof(double);
   if (vec) hipLaunchKernelGGL((outconv_bwd_kernel<T, true>), grid, dim3(256), lds, stream, dz_only, dp, p, t, sums, alpha, beta, gamma, smooth, gscale, h, h_nstride, w, dh, dh_nstride, part, loss, C, S, fpart, fnp);

@@ -1982,6 +1982,10 @@ int pw_bwd_tail_impl(const float* dout, long long dout_nstride, const T* out, lo
                      hipStream_t stream, const float* dscale = nullptr, const float* dpool = nullptr,
                      long long dpns = 0, const unsigned char* pidx = nullptr, int Hf = 0, int Wf = 0) {
   L3U_REQUIRE(N > 0 && l3u_pw_bwd_supported(J, K, S) && !pw_bwd_wide(J));
+  // one dout form: the pool-fold variants carry no dscale code.  Defensive only here: no entry
+  // point of this launcher passes both (_r1 gives dscale alone, _up dpool alone); the pair
+  // launcher below is the one the C ABI can reach with both
+  L3U_REQUIRE(!(dscale && dpool));
   L3U_REQUIRE(dpool == nullptr || (pidx && Hf % 2 == 0 && Wf % 4 == 0 && (S / (Hf * Wf)) % 2 == 0 &&
                                    dpns % 2 == 0 && ((uintptr_t)dpool & 7) == 0));
   L3U_REQUIRE(dout && out && yr && rec && tail_part && npart > 0 && (sel == 1 || sel == 2));
@@ -2030,6 +2034,7 @@ int pw_bwd_tail_pair_impl(const float* dout, long long dout_nstride, const float
                           int S, hipStream_t stream) {
   L3U_REQUIRE(N > 0 && a.K > 0 && b.K > 0 && l3u_pw_bwd_supported(J, a.K, S) &&
               l3u_pw_bwd_supported(J, b.K, S) && !pw_bwd_wide(J));
+  L3U_REQUIRE(!(dscale && dpool));   // one dout form: the pool-fold variants carry no dscale code
   L3U_REQUIRE(dpool == nullptr || (pidx && Hf % 2 == 0 && Wf % 4 == 0 && (S / (Hf * Wf)) % 2 == 0 &&
                                    dpns % 2 == 0 && ((uintptr_t)dpool & 7) == 0));
   L3U_REQUIRE(dout && out && tail_part && npart > 0);

@@ -283,6 +283,83 @@ def test_pw_bwd_tail_twin(cuda, case):
                   f"pw_bwd_tail dW sel{sel}")
 
 
+@pytest.mark.parametrize("form", ["plain", "r1", "up"])
+@pytest.mark.parametrize("case", [(2, 16, 16, (6, 8, 12)), (2, 32, 16, (10, 20, 24))])
+def test_tail_family_twins(cuda, case, form):
+    """The block-tail backward family by dout form (tests/test_tail_bwd_gpu.py has the fp64
+    reference of the fp32 entry points): l3u_norm_act_bwd_reduce[_r1|_up]_bf16,
+    l3u_pw_bwd_tail[_r1|_up]_bf16 (sel 1, then sel 2 accumulating) and l3u_pw_bwd_tail_pair_bf16
+    beside their fp32 twins, with test_norm_act_twins' bound on the tail sums and
+    test_pw_bwd_tail_twin's on dx / dW; the bf16 pair equals its two bf16 calls bit for bit."""
+    N, J, K, (D, H, W) = case
+    S, So = D * H * W, D * H * W // 8
+    gen = torch.Generator().manual_seed(70)
+    tw = Twin(cuda)
+    out, y2, r, z2, lev = (tw.act(torch.randn(N, J, S, generator=gen)) for _ in range(5))
+    x = tw.act(torch.randn(N, K, S, generator=gen))
+    rec2, recr = make_rec(N, J, gen).to(cuda), make_rec(N, J, gen).to(cuda)
+    W2, Wr = torch.randn(J, J, generator=gen).to(cuda), torch.randn(J, K, generator=gen).to(cuda)
+    init = torch.randn(N, K, S, generator=gen)
+    dsc = dpool = idx = None
+    if form == "r1":
+        dsrc, dns = torch.randn(N, 1, S, generator=gen).to(cuda), S
+        dsc = torch.randn(J, generator=gen).to(cuda)
+    else:
+        dsrc, dns = torch.randn(N, J, S, generator=gen).to(cuda), J * S
+    if form == "up":
+        dpool = torch.randn(N, J, So, generator=gen).to(cuda)
+        pooled = tw.out((N, J, So))
+        ix = {dt: torch.empty(N * J * So, dtype=torch.uint8, device=cuda) for dt in DT}
+        for dt in DT:
+            nat().call("l3u_maxpool2_fwd" + sfx(dt), P(lev[dt]), J * S, P(pooled[dt]), J * So, P(ix[dt]),
+                       N, J, D, H, W, st())
+        torch.cuda.synchronize()
+        assert torch.equal(ix[BF], ix[torch.float32])
+        idx = ix[BF]
+    head = {"plain": (P(dsrc), dns), "r1": (P(dsrc), dns, P(dsc)),
+            "up": (P(dsrc), dns, P(dpool), J * So, P(idx))}[form]
+    dims = (D, H, W) if form == "up" else (S,)
+    ext = {"plain": "", "r1": "_r1", "up": "_up"}[form]
+    nb = nat().query("l3u_norm_act_nblocks", S)
+    tp = {dt: torch.full((J * N * nb * 3,), float("nan"), dtype=torch.float64, device=cuda) for dt in DT}
+    for dt in DT:
+        nat().call("l3u_norm_act_bwd_reduce" + ext + sfx(dt), *head, P(out[dt]), J * S, P(y2[dt]), J * S,
+                   P(rec2), P(r[dt]), J * S, P(recr), P(tp[dt]), N, J, *dims, st())
+    torch.cuda.synchronize()
+    check_f32(tp[BF], tp[torch.float32], 1e-9, f"tail sums {form}")
+    npa = nat().query("l3u_pw_bwd_nparts", N, J, J, S)
+    npb = nat().query("l3u_pw_bwd_nparts", N, J, K, S)
+    res = {}
+    for mode in ("single", "pair"):
+        dxa, dxb = tw.gout((N, J, S)), tw.gout((N, K, S), init)
+        pa = {dt: torch.full((npa * J * J,), float("nan"), device=cuda) for dt in DT}
+        pb = {dt: torch.full((npb * J * K,), float("nan"), device=cuda) for dt in DT}
+        for dt in DT:
+            if mode == "single":
+                for sel, yr, rec, xin, w, dx, acc, part, K_ in (
+                        (1, y2, rec2, z2, W2, dxa, 0, pa, J), (2, r, recr, x, Wr, dxb, 1, pb, K)):
+                    nat().call("l3u_pw_bwd_tail" + ext + sfx(dt), *head, P(out[dt]), J * S, P(yr[dt]),
+                               J * S, P(rec), P(tp[dt]), nb, sel, P(xin[dt]), K_ * S, P(w), P(dx[dt]),
+                               K_ * S, acc, P(part[dt]), N, J, K_, *dims, st())
+            else:
+                nat().call("l3u_pw_bwd_tail_pair" + sfx(dt), P(dsrc), dns, P(dsc), P(dpool),
+                           J * So if form == "up" else 0, P(idx), H if form == "up" else 0,
+                           W if form == "up" else 0, P(out[dt]), J * S, P(tp[dt]), nb,
+                           P(y2[dt]), J * S, P(rec2), P(z2[dt]), J * S, P(W2), P(dxa[dt]), J * S, 0,
+                           P(pa[dt]), J, 1,
+                           P(r[dt]), J * S, P(recr), P(x[dt]), K * S, P(Wr), P(dxb[dt]), K * S, 1,
+                           P(pb[dt]), K, 2, N, J, S, st())
+        torch.cuda.synchronize()
+        for name, dx, part, np_, K_ in (("sel1", dxa, pa, npa, J), ("sel2", dxb, pb, npb, K)):
+            assert torch.isfinite(dx[BF]).all() and torch.isfinite(part[BF]).all()
+            check_f32(dx[BF], dx[torch.float32], 1e-6, f"tail{ext} {mode} dx {name}")
+            check_f32(part[BF].view(np_, J, K_).sum(0), part[torch.float32].view(np_, J, K_).sum(0),
+                      1e-5, f"tail{ext} {mode} dW {name}")
+        res[mode] = (dxa[BF], dxb[BF], pa[BF], pb[BF])
+    for a, b in zip(res["single"], res["pair"]):
+        assert torch.equal(a, b)
+
+
 @pytest.mark.parametrize("case", [(4, 128, 64, 6, 6, 6), (4, 64, 32, 12, 12, 12), (4, 32, 16, 24, 24, 24),
                                   (1, 8, 4, 5, 7, 9), (2, 128, 64, 16, 16, 16)])
 def test_convt_twin(cuda, case):
@@ -424,6 +501,45 @@ def test_outconv_twin(cuda, case):
     torch.cuda.synchronize()
     check_f32(dh[BF], dh[torch.float32], 1e-6, "outconv dh")
     assert torch.equal(part[BF], part[torch.float32])
+
+
+@pytest.mark.parametrize("case", [(2, 16, 6 * 8 * 12), (1, 8, 37)])
+def test_outconv_dz_twins(cuda, case):
+    """l3u_outconv_bwd_dz_bf16 and l3u_outconv_bwd_ftl_dz_bf16 beside their fp32 twins (dz =
+    d(pre-sigmoid), the rank-1 dout of the last block's tail) at test_outconv_twin's bounds; the
+    two bf16 forms agree bit for bit, as the fp32 ones do."""
+    N, C, S = case
+    gen = torch.Generator().manual_seed(73)
+    tw = Twin(cuda)
+    h = tw.act(torch.randn(N, C, S, generator=gen))
+    w = (torch.randn(C, generator=gen) * 0.3).to(cuda)
+    b = torch.randn(1, generator=gen).to(cuda)
+    t = (torch.rand(N, S, generator=gen) > 0.9).float().to(cuda)
+    nb = nat().query("l3u_outconv_nblocks", S)
+    p = torch.empty(N, S, device=cuda)
+    fp = torch.empty(N * nb * 3, device=cuda)
+    nat().call("l3u_outconv_fwd_bf16", P(h[BF]), C * S, P(w), P(b), P(p), P(t), P(fp), N, C, S, st())
+    sums = torch.empty(3, dtype=torch.float64, device=cuda)
+    nat().call("l3u_ftl_reduce", P(fp), N * nb, P(sums), st())
+    abgs = (0.7, 0.3, 0.75, 1e-6)
+    res = {}
+    for ftl in (False, True):
+        dz = tw.gout((N, 1, S))
+        part = {dt: torch.full((N * nb * (C + 1),), float("nan"), dtype=torch.float64, device=cuda)
+                for dt in DT}
+        loss = {dt: torch.full((), float("nan"), device=cuda) for dt in DT}
+        for dt in DT:
+            src = (P(fp), N * nb) if ftl else (P(sums),)
+            nat().call("l3u_outconv_bwd_ftl_dz" + sfx(dt) if ftl else "l3u_outconv_bwd_dz" + sfx(dt),
+                       *(() if ftl else (None,)), P(p), P(t), *src, *abgs, None, P(h[dt]), C * S, P(w),
+                       P(dz[dt]), S, P(part[dt]), P(loss[dt]), N, C, S, st())
+        torch.cuda.synchronize()
+        assert torch.isfinite(dz[BF]).all() and torch.isfinite(part[BF]).all()
+        check_f32(dz[BF], dz[torch.float32], 1e-6, f"outconv dz ftl={ftl}")
+        assert torch.equal(part[BF], part[torch.float32]) and torch.equal(loss[BF], loss[torch.float32])
+        res[ftl] = (dz[BF], part[BF], loss[BF])
+    for a, c in zip(res[False], res[True]):
+        assert torch.equal(a, c)
 
 
 @pytest.mark.parametrize("shape", [(4, 16, 48, 48, 48), (2, 8, 5, 6, 8)])

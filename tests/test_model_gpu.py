@@ -119,6 +119,58 @@ def test_dropout_masks_match_oracle(cuda, golden):
     assert np.abs(pe.cpu().numpy() - z["out"]).max() <= 1e-3
 
 
+def test_dropout_gradients_match_oracle(cuda, golden):
+    """Dropout3d on (p = 0.1, what bench.py times): the training step's output, loss and parameter
+    gradients against the fp64 oracle fed the kernels' own keep masks, under this module's
+    gradient rule with e32 the fp32 CPU oracle's error on the same inputs and masks."""
+    from light_unet.models.unet3d import Lightweight3DUNet
+    from light_unet.train_step import TrainStep
+    z = golden("model_b2_32.npz")
+    sd = {k[2:]: torch.from_numpy(z[k]) for k in z.files if k.startswith("w/")}
+    x = torch.from_numpy(z["x"]).to(cuda)
+    t = torch.from_numpy(z["target"]).to(cuda)
+    m = Lightweight3DUNet(dropout_p=0.1)
+    m.load_state_dict(sd)
+    m = m.to(cuda).train()
+    ts = TrainStep(m)
+    p, sv, sums = ts._fwd(x, t)
+    masks, blocks_with_drop = {}, 0
+    for name, b in sv["blk"].items():
+        k = b["recs"][1].view(x.shape[0], -1, 8)[..., 4].cpu()
+        uk = np.unique(k.numpy())
+        assert all(np.isclose(v, 0.0) or np.isclose(v, 1 / 0.9, rtol=1e-6) for v in uk), uk
+        masks[name] = (k > 0).double()
+        blocks_with_drop += int((k == 0).any())
+    # a mask that drops nothing would make the comparison the p = 0 one
+    assert blocks_with_drop >= 3, blocks_with_drop
+    ts._bwd(p, sv, t, sums)   # (also applies the AdamW update: the weights are taken from sd)
+    torch.cuda.synchronize()
+    grads = {k: ts.gflat[off:off + n].view(shape).cpu().numpy()
+             for k, (off, n, shape) in m.param_slices().items()}
+
+    def oracle(dt):
+        params = {k: v.clone().to(dt).requires_grad_(True) for k, v in sd.items()}
+        out = U.unet_forward(params, torch.from_numpy(z["x"]).to(dt),
+                             drop_masks={k: v.to(dt) for k, v in masks.items()}, drop_p=0.1)
+        loss = U.focal_tversky(out, torch.from_numpy(z["target"]).to(dt))
+        loss.backward()
+        return out.detach(), loss.detach(), {k: q.grad.numpy() for k, q in params.items()}
+
+    o64, l64, g64 = oracle(torch.float64)
+    _, _, g32 = oracle(torch.float32)
+    ref = {"g/" + k: v for k, v in g64.items()}
+    oerr = np.abs(p.cpu().numpy() - o64.numpy()).max()
+    assert oerr <= 1e-3, oerr
+    assert abs(ts.loss.item() - float(l64)) <= 1e-4 * abs(float(l64)), (ts.loss.item(), float(l64))
+    errs, gerr = _grad_errs(grads, ref)
+    e32, ge32 = _grad_errs(g32, ref)
+    print(f"dropout 0.1: out err {oerr:.2e}, grad L2 err {gerr:.2e} (cpu fp32 {ge32:.2e}), worst "
+          f"tensor {max(errs.items(), key=lambda kv: kv[1])}, {blocks_with_drop} blocks drop")
+    assert gerr <= max(1e-3, 2 * ge32), (gerr, ge32)
+    bad = {k: (errs[k], e32[k]) for k in errs if errs[k] > max(1e-2, 3 * e32[k])}
+    assert not bad, f"gradient errors above tolerance: {bad}"
+
+
 def test_backward_is_deterministic(cuda, golden):
     z = golden("model_b2_32.npz")
     model, _ = _model(z, (16, 32, 64, 128), cuda)

@@ -730,12 +730,16 @@ def test_convt_fwd_fused(cuda, case):
     assert torch.all(cat[:, Co:] == 7.0)
 
 
-@pytest.mark.parametrize("case", [(2, 16, 4096), (3, 16, 1000), (1, 8, 37)])
+@pytest.mark.parametrize("case", [(2, 16, 4096), (3, 16, 1000), (1, 8, 37),
+                                  # t and p one element into their storage (4-byte aligned only:
+                                  # the 16-byte vector loads / stores must not be taken)
+                                  (2, 16, 4096, 1)])
 def test_outconv_ftl_fused(cuda, case):
     """out_conv forward emitting the FocalTversky partials, and its backward forming dL/dp from
     the global sums in-kernel, vs the oracle (losses.py:30-54 autograd) in fp64."""
     from oracle.unet_oracle import focal_tversky
-    N, C, S = case
+    N, C, S = case[:3]
+    off = case[3] if len(case) > 3 else 0
     gen = torch.Generator().manual_seed(12)
     h = torch.randn(N, C, S, generator=gen, dtype=torch.float64)
     w = torch.randn(1, C, generator=gen, dtype=torch.float64) * 0.3
@@ -745,10 +749,13 @@ def test_outconv_ftl_fused(cuda, case):
     p = torch.sigmoid(torch.einsum("oc,ncs->nos", wr, hr) + br[None, :, None])
     loss = focal_tversky(p, t)
     loss.backward()
-    hd, wd, bd, td = h.float().to(cuda), w.float().to(cuda), b.float().to(cuda), t.float().to(cuda)
+    hd, wd, bd = h.float().to(cuda), w.float().to(cuda), b.float().to(cuda)
+    td = torch.empty(N * S + off, device=cuda)[off:].view(N, 1, S)
+    td.copy_(t.float())
     nb = nat().query("l3u_outconv_nblocks", S)
     fpart = torch.full((N * nb * 3,), float("nan"), device=cuda)
-    pd = torch.empty(N, 1, S, device=cuda)
+    pd = torch.empty(N * S + off, device=cuda)[off:].view(N, 1, S)
+    assert td.data_ptr() % 16 == 4 * off and pd.data_ptr() % 16 == 4 * off
     nat().call("l3u_outconv_fwd", hd.data_ptr(), C * S, wd.data_ptr(), bd.data_ptr(), pd.data_ptr(),
                td.data_ptr(), fpart.data_ptr(), N, C, S, st())
     sums = torch.empty(3, dtype=torch.float64, device=cuda)
@@ -1099,3 +1106,152 @@ def test_box_copy_pad_and_crop(cuda, dt):
     assert torch.equal(cat[:, :C], ref)
     assert torch.all(cat[:, C:] == 7.0)
     assert torch.equal(back, src)
+
+
+# ------------------------------------------------------------------------------ rank-1 operands
+# (include/l3u.h "Rank-1 operands": a negative batch stride, channel c = record[c][7] * the one
+# stored channel) against the fp64 references of the materialised tensor
+
+def _rank1(N, C, S, gen):
+    """one stored channel z [N][1][S], the scales rk [C] and the materialised float products"""
+    z = torch.randn(N, 1, S, generator=gen)
+    rk = 1 + 0.3 * torch.randn(C, generator=gen)
+    return z, rk, (rk[None, :, None] * z).double()
+
+
+# the two smallest volumes l3u_dw3_bwd_rank1 offers (D = 2; odd D = 3: both with H = 4 below the
+# row strip of 64 / (W / 4) rows), and one with two row strips (the second ragged: H = 14, strips
+# of 10), odd D and several z chunks
+DW_RANK1_SHAPES = [(2, 4, 2, 4, 24), (2, 3, 3, 4, 20), (1, 4, 9, 14, 24)]
+
+
+@pytest.mark.parametrize("shape", DW_RANK1_SHAPES)
+def test_dw3_bwd_rank1_input(cuda, shape):
+    """l3u_dw3_bwd with a rank-1 IN-fused x (the first block's y1 = w1[c] * z1, with the Dropout3d
+    scale in the record) vs the mode-1 reference of test_dw3_bwd on the materialised tensor."""
+    N, C, D, H, W = shape
+    assert nat().query("l3u_dw3_bwd_rank1", N, C, D, H, W) == 1
+    S = D * H * W
+    gen = torch.Generator().manual_seed(21)
+    z, rk, xm = _rank1(N, C, S, gen)
+    x = xm.view(N, C, D, H, W)
+    w = torch.randn(C, 1, 3, 3, 3, generator=gen, dtype=torch.float64)
+    dz = torch.randn(shape, generator=gen, dtype=torch.float64)
+    rec = make_rec(N, C, gen, drop=True)
+    wr = w.clone().requires_grad_(True)
+    k = rec[..., 4][:, :, None, None, None]
+    sc = (rec[..., 1] * rec[..., 5])[:, :, None, None, None]
+    sh = (rec[..., 6] - rec[..., 5] * rec[..., 1] * rec[..., 0])[:, :, None, None, None]
+    pre = (sc * x + sh).requires_grad_(True)
+    F.conv3d(k * F.leaky_relu(pre, SLOPE), wr, padding=1, groups=C).backward(dz)
+    xhat = (x - rec[..., 0][:, :, None, None, None]) * rec[..., 1][:, :, None, None, None]
+    s1_ref = pre.grad.sum(dim=(2, 3, 4))
+    s2_ref = (pre.grad * xhat).sum(dim=(2, 3, 4))
+    nch = nat().query("l3u_dw3_nchunk", N, C, D, H, W)
+    rec[..., 7] = rk.double()[None, :]
+    zd, dzd, recd = z.to(cuda), dz.float().to(cuda), rec.float().to(cuda)
+    wd = w.float().reshape(C, 27).to(cuda)
+    dx = torch.full((N, C, S), float("nan"), device=cuda)
+    dwp = torch.full((C * N * nch * 27,), float("nan"), device=cuda)
+    inp = torch.full((C * N * nch * 2,), float("nan"), dtype=torch.float64, device=cuda)
+    nat().call("l3u_dw3_bwd", dzd.data_ptr(), C * S, zd.data_ptr(), -S, wd.data_ptr(), recd.data_ptr(),
+               dx.data_ptr(), C * S, 0, dwp.data_ptr(), inp.data_ptr(), N, C, D, H, W, st())
+    torch.cuda.synchronize()
+    assert torch.isfinite(dx).all() and torch.isfinite(dwp).all() and torch.isfinite(inp).all()
+    close(dwp.view(C, N * nch, 27).double().sum(1).view(C, 1, 3, 3, 3), wr.grad, 1e-5, f"dW {shape}")
+    close(dx.view(shape), pre.grad, 2e-6, f"dpre {shape}")
+    ip = inp.view(C, N, nch, 2).sum(2)
+    close(ip[..., 0].t(), s1_ref, 1e-5, "sum dpre")
+    close(ip[..., 1].t(), s2_ref, 1e-5, "sum dpre*xhat")
+
+
+@pytest.mark.parametrize("acc", [False, True])
+@pytest.mark.parametrize("case", [(2, 16, 6 * 8 * 10), (1, 16, 10 * 12 * 20)])
+def test_pw_bwd_k1_rank1_y(cuda, case, acc):
+    """l3u_pw_bwd with K = 1 and a rank-1 y (the first block's conv1.pointwise: y1 = w1[c] * z1,
+    never stored) vs the test_pw_bwd_fused reference on the materialised y."""
+    N, J, S = case
+    K = 1
+    assert nat().query("l3u_pw_bwd_supported", J, K, S) == 1
+    gen = torch.Generator().manual_seed(22)
+    z, rk, y = _rank1(N, J, S, gen)
+    x = torch.randn(N, K, S, generator=gen, dtype=torch.float64)
+    w = torch.randn(J, K, generator=gen, dtype=torch.float64)
+    dpre = torch.randn(N, J, S, generator=gen, dtype=torch.float64)
+    g = 1 + 0.3 * torch.randn(J, generator=gen, dtype=torch.float64)
+    yr = y.clone().requires_grad_(True)
+    F.instance_norm(yr, weight=g, eps=1e-5).backward(dpre)
+    dy = yr.grad
+    m = y.mean(-1)
+    rs = 1 / torch.sqrt(y.var(-1, unbiased=False) + 1e-5)
+    rec = torch.zeros(N, J, 8, dtype=torch.float64)
+    rec[..., 0], rec[..., 1], rec[..., 5], rec[..., 7] = m, rs, g.expand(N, J), rk.double().expand(N, J)
+    xhat = (y - m[..., None]) * rs[..., None]
+    nch = 3
+    part_in = torch.zeros(J, N, nch, 2, dtype=torch.float64)
+    part_in[:, :, 1, 0] = dpre.sum(-1).t()
+    part_in[:, :, 1, 1] = (dpre * xhat).sum(-1).t()
+    dx0 = torch.randn(N, K, S, generator=gen, dtype=torch.float64) if acc else torch.zeros(N, K, S,
+                                                                                            dtype=torch.float64)
+    ref_dx = torch.einsum("jk,njs->nks", w, dy) + dx0
+    ref_dw = torch.einsum("njs,nks->jk", dy, x)
+    P = nat().query("l3u_pw_bwd_nparts", N, J, K, S)
+    part = torch.full((P * J * K,), float("nan"), device=cuda)
+    xd, wd, dd, zd = x.float().to(cuda), w.float().to(cuda), dpre.float().to(cuda), z.to(cuda)
+    recd, pid = rec.float().to(cuda), part_in.to(cuda)
+    dx = dx0.float().to(cuda) if acc else torch.full((N, K, S), float("nan"), device=cuda)
+    nat().call("l3u_pw_bwd", dd.data_ptr(), J * S, zd.data_ptr(), -S, recd.data_ptr(), pid.data_ptr(),
+               nch, xd.data_ptr(), K * S, wd.data_ptr(), dx.data_ptr(), K * S, 1 if acc else 0,
+               part.data_ptr(), N, J, K, S, st())
+    torch.cuda.synchronize()
+    assert torch.isfinite(dx).all() and torch.isfinite(part).all()
+    close(dx, ref_dx, 1e-5, f"pw_bwd rank-1 dx {case}")
+    close(part.view(P, J, K).double().sum(0), ref_dw, 2e-5, f"pw_bwd rank-1 dw {case}")
+
+
+@pytest.mark.parametrize("shape", [(2, 16, 6, 8, 12), (2, 12, 10, 20, 24)])
+def test_norm_act_fwd_rank1_r(cuda, shape):
+    """l3u_norm_act_fwd and l3u_norm_act_pool_fwd with a rank-1 residual (the first block's
+    shortcut r = wsc[c] * x, one stored channel) vs the fp64 block-tail forward."""
+    N, C, D, H, W = shape
+    S, So = D * H * W, D * H * W // 8
+    gen = torch.Generator().manual_seed(23)
+    xs, wsc, r = _rank1(N, C, S, gen)
+    y2 = torch.randn(N, C, S, generator=gen).double()
+    g2, b2, gr, br = (a + 0.3 * torch.randn(C, generator=gen, dtype=torch.float64) for a in (1, 0, 1, 0))
+    ref = F.leaky_relu(F.instance_norm(y2, weight=g2, bias=b2, eps=1e-5) +
+                       F.instance_norm(r, weight=gr, bias=br, eps=1e-5), SLOPE)
+
+    def rec_of(v, g, b):
+        m = v.mean(-1)
+        rs = 1 / torch.sqrt(v.var(-1, unbiased=False) + 1e-5)
+        rc = torch.zeros(N, C, 8, dtype=torch.float64)
+        rc[..., 0], rc[..., 1] = m, rs
+        rc[..., 2] = g * rs
+        rc[..., 3] = b
+        rc[..., 4], rc[..., 5], rc[..., 6] = 1, g.expand(N, C), b.expand(N, C)
+        return rc
+
+    rec2 = rec_of(y2, g2, b2).float().to(cuda)
+    recr = rec_of(r, gr, br)
+    recr[..., 7] = wsc.double()[None, :]
+    recr = recr.float().to(cuda)
+    y2d, xd = y2.float().to(cuda), xs.to(cuda)
+    o1 = torch.full((N, C, S), float("nan"), device=cuda)
+    o2 = torch.full((N, C, S), float("nan"), device=cuda)
+    pooled = torch.full((N, C, So), float("nan"), device=cuda)
+    idx = torch.empty(N, C, So, dtype=torch.uint8, device=cuda)
+    nat().call("l3u_norm_act_fwd", y2d.data_ptr(), C * S, rec2.data_ptr(), None, xd.data_ptr(), -S,
+               recr.data_ptr(), None, 1, o1.data_ptr(), C * S, N, C, S, st())
+    nat().call("l3u_norm_act_pool_fwd", y2d.data_ptr(), C * S, rec2.data_ptr(), None, xd.data_ptr(), -S,
+               recr.data_ptr(), None, 1, o2.data_ptr(), C * S, pooled.data_ptr(), C * So,
+               idx.data_ptr(), N, C, D, H, W, st())
+    p3 = torch.empty_like(pooled)
+    i3 = torch.empty_like(idx)
+    nat().call("l3u_maxpool2_fwd", o2.data_ptr(), C * S, p3.data_ptr(), C * So, i3.data_ptr(), N, C,
+               D, H, W, st())
+    torch.cuda.synchronize()
+    close(o1, ref, 2e-6, f"norm_act_fwd rank-1 r {shape}")
+    close(o2, ref, 2e-6, f"norm_act_pool_fwd rank-1 r {shape}")
+    close(pooled, F.max_pool3d(ref.view(N, C, D, H, W), 2).view(N, C, So), 2e-6, "pooled")
+    assert torch.equal(pooled, p3) and torch.equal(idx, i3)
