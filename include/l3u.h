@@ -452,6 +452,66 @@ int l3u_ftl_bwd(const float* p, const float* t, long long numel, const double* s
                 double beta, double gamma, double smooth, const float* gscale,
                 int through_sigmoid, float* g, hipStream_t stream);
 
+/* ---- The loss family on four sums: FocalTverskyLoss, CombinedLoss, DiceLoss -----------------
+ * (light_unet/models/losses.py:11-54, :57-85, :88-113; get_loss_function :116-147)
+ * sums[4] (fp64, fixed order) = {sum p*t, sum p, sum t, sum e} over ALL voxels of the batch, with
+ * e_i = -(t max(ln p, -100) + (1 - t) max(ln(1 - p), -100)) as nn.BCELoss forms it (losses.py:83).
+ *   L = w_ftl (1 - TI)^gamma + w_bce sums[3] / global_numel
+ *       + w_dice (1 - (2 s0 + smooth_dice) / U),
+ *   U = s1 + s2 + smooth_dice;  TI, alpha, beta, gamma, smooth_ftl as in l3u_ftl_loss.
+ *   dL/dp_i = cA t_i + cB (1 - t_i) + cE (p_i - t_i) / max(p_i (1 - p_i), 1e-12),
+ *   cA = w_ftl A + w_dice (Q - 2 / U), cB = w_ftl B + w_dice Q, Q = (2 s0 + smooth_dice) / U^2,
+ *   cE = w_bce / global_numel (torch's binary_cross_entropy_backward).
+ * The descriptor is nine plain scalars; global_numel is the GLOBAL element count (all ranks'
+ * voxels under the exact data-parallel mode).  FocalTverskyLoss = (1, a, b, g, s, 0, M, 0, 0),
+ * CombinedLoss = (ftl_weight, a, b, g, 1e-6, bce_weight, M, 0, 0), DiceLoss = (0, .., 0, M, 1,
+ * smooth).  A term
+ * whose weight is 0 is not evaluated.  Part buffers hold [l3u_ftl_nblocks(numel)][4] floats
+ * (l3u_loss4_sums) or [N * l3u_outconv_nblocks(S)][4] (l3u_outconv_fwd_loss4); columns 0-2 are
+ * bit-identical to the three-column FocalTversky forms.  No allocation, no atomics.           */
+int l3u_loss4_sums(const float* p, const float* t, long long numel, float* part, double* sums,
+                   hipStream_t stream);
+int l3u_loss4_reduce(const float* part, int nparts, double* sums, hipStream_t stream);
+int l3u_loss4_value(const double* sums,
+    double w_ftl, double alpha, double beta, double gamma, double smooth_ftl, double w_bce,
+    double global_numel, double w_dice, double smooth_dice,
+    float* loss, hipStream_t stream);
+int l3u_loss4_bwd(const float* p, const float* t, long long numel, const double* sums,
+    double w_ftl, double alpha, double beta, double gamma, double smooth_ftl, double w_bce,
+    double global_numel, double w_dice, double smooth_dice,
+    const float* gscale, int through_sigmoid, float* g, hipStream_t stream);
+/* l3u_outconv_fwd (unet3d.py:220-221) with the four-column partials ftl_part[N*nblocks][4]
+ * (losses.py:40-42, :83, :108-109); t must be given.  The float4 path is taken only when
+ * S % 4 == 0, h_nstride % 4 == 0 and h, p, t are 16-byte aligned; otherwise the scalar path.  */
+int l3u_outconv_fwd_loss4(const float* h, long long h_nstride, const float* w, const float* b,
+    float* p, const float* t, float* ftl_part, int N, int C, int S, hipStream_t stream);
+/* l3u_outconv_bwd / l3u_outconv_bwd_dz with the family descriptor in place of (alpha, beta,
+ * gamma, smooth) and sums[4] (losses.py:82-85, :108-113); the loss gradient is always formed in
+ * the launch (no dp form).  The float4 path needs 16-byte aligned p, t, h, dh as well.         */
+int l3u_outconv_bwd_loss4(const float* p, const float* t, const double* sums,
+    double w_ftl, double alpha, double beta, double gamma, double smooth_ftl, double w_bce,
+    double global_numel, double w_dice, double smooth_dice,
+    const float* gscale, const float* h, long long h_nstride, const float* w, float* dh,
+    long long dh_nstride, double* part, float* loss, int N, int C, int S, hipStream_t stream);
+int l3u_outconv_bwd_loss4_dz(const float* p, const float* t, const double* sums,
+    double w_ftl, double alpha, double beta, double gamma, double smooth_ftl, double w_bce,
+    double global_numel, double w_dice, double smooth_dice,
+    const float* gscale, const float* h, long long h_nstride, const float* w, float* dh,
+    long long dh_nstride, double* part, float* loss, int N, int C, int S, hipStream_t stream);
+/* the partial-reducing forms (l3u_outconv_bwd_ftl / _ftl_dz for the family): every workgroup
+ * reduces loss_part[loss_nparts][4] itself in l3u_loss4_reduce's order, so the result is
+ * bit-identical to l3u_loss4_reduce + l3u_outconv_bwd_loss4[_dz] (losses.py:82-85).           */
+int l3u_outconv_bwd_loss4p(const float* p, const float* t, const float* loss_part, int loss_nparts,
+    double w_ftl, double alpha, double beta, double gamma, double smooth_ftl, double w_bce,
+    double global_numel, double w_dice, double smooth_dice,
+    const float* gscale, const float* h, long long h_nstride, const float* w, float* dh,
+    long long dh_nstride, double* part, float* loss, int N, int C, int S, hipStream_t stream);
+int l3u_outconv_bwd_loss4p_dz(const float* p, const float* t, const float* loss_part, int loss_nparts,
+    double w_ftl, double alpha, double beta, double gamma, double smooth_ftl, double w_bce,
+    double global_numel, double w_dice, double smooth_dice,
+    const float* gscale, const float* h, long long h_nstride, const float* w, float* dh,
+    long long dh_nstride, double* part, float* loss, int N, int C, int S, hipStream_t stream);
+
 /* ---- the first block's front (in_channels = 1, unet3d.py:163-167) --------------------------
  * one launch for the Conv1x1 shortcut r[c] = wr[c]*x, conv1.depthwise z1 = dw3(x) (one channel,
  * w_dw [27]) and conv1.pointwise y1[c] = w1[c]*z1, with the (count, mean, M2) partials of r and y1
@@ -587,6 +647,28 @@ int l3u_outconv_bwd_ftl_dz_bf16(const float* p, const float* t, const float* ftl
                                 long long h_nstride, const float* w, float* dh,
                                 long long dh_nstride, double* part, float* loss, int N, int C,
                                 int S, hipStream_t stream);
+int l3u_outconv_fwd_loss4_bf16(const l3u_bf16* h, long long h_nstride, const float* w, const float* b,
+    float* p, const float* t, float* ftl_part, int N, int C, int S, hipStream_t stream);
+int l3u_outconv_bwd_loss4_bf16(const float* p, const float* t, const double* sums,
+    double w_ftl, double alpha, double beta, double gamma, double smooth_ftl, double w_bce,
+    double global_numel, double w_dice, double smooth_dice,
+    const float* gscale, const l3u_bf16* h, long long h_nstride, const float* w, float* dh,
+    long long dh_nstride, double* part, float* loss, int N, int C, int S, hipStream_t stream);
+int l3u_outconv_bwd_loss4_dz_bf16(const float* p, const float* t, const double* sums,
+    double w_ftl, double alpha, double beta, double gamma, double smooth_ftl, double w_bce,
+    double global_numel, double w_dice, double smooth_dice,
+    const float* gscale, const l3u_bf16* h, long long h_nstride, const float* w, float* dh,
+    long long dh_nstride, double* part, float* loss, int N, int C, int S, hipStream_t stream);
+int l3u_outconv_bwd_loss4p_bf16(const float* p, const float* t, const float* loss_part, int loss_nparts,
+    double w_ftl, double alpha, double beta, double gamma, double smooth_ftl, double w_bce,
+    double global_numel, double w_dice, double smooth_dice,
+    const float* gscale, const l3u_bf16* h, long long h_nstride, const float* w, float* dh,
+    long long dh_nstride, double* part, float* loss, int N, int C, int S, hipStream_t stream);
+int l3u_outconv_bwd_loss4p_dz_bf16(const float* p, const float* t, const float* loss_part, int loss_nparts,
+    double w_ftl, double alpha, double beta, double gamma, double smooth_ftl, double w_bce,
+    double global_numel, double w_dice, double smooth_dice,
+    const float* gscale, const l3u_bf16* h, long long h_nstride, const float* w, float* dh,
+    long long dh_nstride, double* part, float* loss, int N, int C, int S, hipStream_t stream);
 int l3u_box_copy_bf16(const l3u_bf16* src, long long src_nstride, int sd, int sh, int sw,
                       l3u_bf16* dst, long long dst_nstride, int dd, int dh, int dw, int oz, int oy,
                       int ox, int N, int C, hipStream_t stream);

@@ -2,6 +2,7 @@
 //   maxpool2_fwd/bwd     nn.MaxPool3d(2, 2)                                   unet3d.py:101
 //   outconv fwd/bwd      out_conv 1x1x1 (+bias) + Sigmoid                      unet3d.py:201-202,220-221
 //   ftl_*                FocalTverskyLoss forward sums / loss / closed-form backward  losses.py:30-54
+//   loss4_*              the FocalTversky / CombinedLoss / DiceLoss family on four sums  losses.py:30-113
 //   adamw                torch.optim.AdamW step on the flat parameter buffer     trainer.py:75-79
 //   reduce_segments      deterministic second stage of every split-K / partial reduction
 #include "common.h"
@@ -72,10 +73,20 @@ __global__ __launch_bounds__(256) void maxpool2_bwd_kernel(
 }
 
 // ---------------------------------------------------------------- out_conv + sigmoid
+// One voxel's binary cross entropy (losses.py:83):
+// -(t max(ln p, -100) + (1 - t) max(ln(1 - p), -100)) as nn.BCELoss forms it from the fp32 p: the
+// clamp comes before the product (0 * -inf never forms), 1 - p is formed in fp32, accurate logf.
+L3U_DEV float bce_term(float pv, float tv) {
+  const float lp = fmaxf(logf(pv), -100.f), lq = fmaxf(logf(1.f - pv), -100.f);
+  return -(tv * lp + (1.f - tv) * lq);
+}
+
 // p = sigmoid(b + sum_c w[c] h[c]); 4 voxels per thread (float4 when VEC).  t != NULL: also the
 // FocalTversky partials of this block, ftl_part[n*nb + blk] = {sum p*t, sum p, sum t} (the loss's
-// first reduction stage fused into the producer of p: losses.py:40-42).
-template <typename T, bool VEC>
+// first reduction stage fused into the producer of p: losses.py:40-42).  L4: a fourth column, the
+// sum of the voxels' binary cross entropy (bce_term; losses.py:83), ftl_part[..][4]; the first
+// three columns keep their order of operations, so they come out bit-identical.
+template <typename T, bool VEC, bool L4 = false>
 __global__ __launch_bounds__(256) void outconv_fwd_kernel(
     const T* __restrict__ h, long long hns, const float* __restrict__ w,
     const float* __restrict__ b, float* __restrict__ p, const float* __restrict__ t,
@@ -119,7 +130,7 @@ __global__ __launch_bounds__(256) void outconv_fwd_kernel(
       if (i0 + q < S) pp[i0 + q] = pv[q];
   }
   if (t == nullptr) return;
-  float spt = 0.f, sp = 0.f, st = 0.f;
+  float spt = 0.f, sp = 0.f, st = 0.f, se = 0.f;
 #pragma unroll
   for (int q = 0; q < 4; ++q) {
     if (i0 + q < S) {
@@ -127,16 +138,19 @@ __global__ __launch_bounds__(256) void outconv_fwd_kernel(
       spt = fmaf(pv[q], tv, spt);
       sp += pv[q];
       st += tv;
+      if (L4) se += bce_term(pv[q], tv);
     }
   }
   spt = block_sum256(spt, red);
   sp = block_sum256(sp, red);
   st = block_sum256(st, red);
+  if (L4) se = block_sum256(se, red);
   if (threadIdx.x == 0) {
-    float* o = ftl_part + ((long long)n * gridDim.x + blockIdx.x) * 3;
+    float* o = ftl_part + ((long long)n * gridDim.x + blockIdx.x) * (L4 ? 4 : 3);
     o[0] = spt;
     o[1] = sp;
     o[2] = st;
+    if (L4) o[3] = se;
   }
 }
 
@@ -193,14 +207,88 @@ L3U_DEV void ftl_lane_sums(const float* __restrict__ part, int nb, double& a, do
   c = wave_sum_d(c);
 }
 
-template <typename T, bool VEC>
+// The four-column form over part[nb][4] = {p*t, p, t, bce}: the same lane stride, the same 8-deep
+// clamped unconditional loads with a select at the add and the same wave_sum_d, so sm[0..2] are
+// ftl_lane_sums's bits for the same first three columns.
+L3U_DEV void loss4_lane_sums(const float* __restrict__ part, int nb, double* sm) {
+  const int l = threadIdx.x & 63;
+  double a = 0.0, b = 0.0, c = 0.0, d = 0.0;
+  constexpr int B = 8;
+  for (int i = l; i < nb; i += B * 64) {
+    float va[B], vb[B], vc[B], vd[B];
+#pragma unroll
+    for (int u = 0; u < B; ++u) {
+      const int j = min(i + u * 64, nb - 1);
+      va[u] = part[j * 4];
+      vb[u] = part[j * 4 + 1];
+      vc[u] = part[j * 4 + 2];
+      vd[u] = part[j * 4 + 3];
+    }
+#pragma unroll
+    for (int u = 0; u < B; ++u) {
+      const bool ok = i + u * 64 < nb;
+      a += ok ? va[u] : 0.f;
+      b += ok ? vb[u] : 0.f;
+      c += ok ? vc[u] : 0.f;
+      d += ok ? vd[u] : 0.f;
+    }
+  }
+  sm[0] = wave_sum_d(a);
+  sm[1] = wave_sum_d(b);
+  sm[2] = wave_sum_d(c);
+  sm[3] = wave_sum_d(d);
+}
+
+// One loss family on the four global sums s0 = sum p t, s1 = sum p, s2 = sum t, s3 = sum bce
+// (losses.py:30-113):  L = w_ftl (1 - TI)^gamma + w_bce s3 / numel + w_dice (1 - (2 s0 + sd) / U),
+// U = s1 + s2 + sd.  FocalTversky is (1, 0, 0), CombinedLoss (ftl_weight, bce_weight, 0), DiceLoss
+// (0, 0, 1).  numel is the GLOBAL element count (nn.BCELoss's mean, losses.py:83).
+struct LossDesc { double w_ftl, alpha, beta, gamma, smooth_ftl, w_bce, numel, w_dice, smooth_dice; };
+// dL/dp_i = A t_i + B (1 - t_i) + E (p_i - t_i) / max(p_i (1 - p_i), 1e-12)   (the last term is
+// torch's binary_cross_entropy_backward)
+struct Loss4Coef { double loss, A, B, E; };
+
+L3U_DEV Loss4Coef loss4_coef(const double* sums, const LossDesc& d) {
+  Loss4Coef r;
+  r.loss = 0.0; r.A = 0.0; r.B = 0.0; r.E = 0.0;
+  // a term with weight 0 is left out (not multiplied by 0): its sums may be degenerate
+  if (d.w_ftl != 0.0) {
+    const FtlCoef f = ftl_coef(sums, d.alpha, d.beta, d.gamma, d.smooth_ftl);
+    r.loss = d.w_ftl * f.loss;
+    r.A = d.w_ftl * f.A;
+    r.B = d.w_ftl * f.B;
+  }
+  if (d.w_bce != 0.0) {
+    r.loss += d.w_bce * sums[3] / d.numel;
+    r.E = d.w_bce / d.numel;
+  }
+  if (d.w_dice != 0.0) {
+    const double U = sums[1] + sums[2] + d.smooth_dice;
+    const double num = 2.0 * sums[0] + d.smooth_dice;
+    const double Q = num / (U * U);
+    r.loss += d.w_dice * (1.0 - num / U);
+    r.A += d.w_dice * (Q - 2.0 / U);
+    r.B += d.w_dice * Q;
+  }
+  return r;
+}
+
+// dL/dp of one voxel from the (scaled) coefficients; the fused out_conv backward and the
+// stand-alone loss4_bwd_kernel share it, so both round identically
+L3U_DEV float loss4_grad(float cAB, float cB, float cE, float pv, float tv) {
+  return fmaf(cAB, tv, cB) + cE * ((pv - tv) / fmaxf(pv * (1.f - pv), 1e-12f));
+}
+
+// L4: the loss family of `fam` in place of FocalTversky(alpha, beta, gamma, smooth): sums[4] or
+// fpart[fnp][4], and the binary cross entropy term in dL/dp.
+template <typename T, bool VEC, bool L4 = false>
 __global__ __launch_bounds__(256) void outconv_bwd_kernel(
     int dz_only, const float* __restrict__ dp, const float* __restrict__ p, const float* __restrict__ t,
     const double* __restrict__ sums, double alpha, double beta, double gamma, double smooth,
     const float* __restrict__ gscale, const T* __restrict__ h, long long hns,
     const float* __restrict__ w, float* __restrict__ dh, long long dhns,
     double* __restrict__ part, float* __restrict__ loss, int C, int S,
-    const float* __restrict__ fpart = nullptr, int fnp = 0) {
+    const float* __restrict__ fpart = nullptr, int fnp = 0, LossDesc fam = LossDesc()) {
   L3U_STAMP_SCOPE(404);
   extern __shared__ double redd[];   // [4][C+1]
   const int n = blockIdx.y, nb = gridDim.x;
@@ -223,8 +311,23 @@ __global__ __launch_bounds__(256) void outconv_bwd_kernel(
       if (c < C && i0 < S) hv[c] = ldv4(hp + (long long)c * S + i0);
     }
   }
-  float cA = 0.f, cB = 0.f;
-  if (dp == nullptr) {
+  float cA = 0.f, cB = 0.f, cE = 0.f;
+  if (L4 && dp == nullptr) {
+    // the same prologue for the family: per wave, no LDS hand-off, no barrier
+    double sm[4];
+    if (fpart != nullptr) {
+      loss4_lane_sums(fpart, fnp, sm);
+    } else {
+      sm[0] = sums[0]; sm[1] = sums[1]; sm[2] = sums[2]; sm[3] = sums[3];
+    }
+    const Loss4Coef r = loss4_coef(sm, fam);
+    const double s = gscale ? (double)gscale[0] : 1.0;
+    cA = (float)(r.A * s);
+    cB = (float)(r.B * s);
+    cE = (float)(r.E * s);
+    if (loss && blockIdx.x == 0 && blockIdx.y == 0 && threadIdx.x == 0) loss[0] = (float)r.loss;
+  }
+  if (!L4 && dp == nullptr) {
     // every wave forms the coefficients itself (no LDS hand-off, no barrier).  fpart: the
     // FocalTversky sums from the out_conv forward's partials in ftl_sums_kernel's order
     // (bit-identical to l3u_ftl_reduce; wave_sum_d leaves the same total in every lane)
@@ -246,7 +349,7 @@ __global__ __launch_bounds__(256) void outconv_bwd_kernel(
     if (i0 + q < S) {
       const float pv = VEC ? pv4[q] : p[o + i0 + q];
       const float gs = VEC ? gv4[q] : (dp ? dp[o + i0 + q] : t[o + i0 + q]);
-      const float g = dp ? gs : fmaf(cA - cB, gs, cB);
+      const float g = dp ? gs : (L4 ? loss4_grad(cA - cB, cB, cE, pv, gs) : fmaf(cA - cB, gs, cB));
       dz[q] = g * pv * (1.f - pv);
     }
   }
@@ -357,6 +460,73 @@ __global__ __launch_bounds__(256) void ftl_bwd_kernel(
     const float tv = t[i];
     float v = fmaf(A - B, tv, B);
     if (through_sigmoid) { const float pv = p[i]; v *= pv * (1.f - pv); }
+    g[i] = v;
+  }
+}
+
+// ---------------------------------------------------------------- the loss family on four sums
+// part[blk] = {sum p*t, sum p, sum t, sum bce}
+__global__ __launch_bounds__(256) void loss4_partials_kernel(const float* __restrict__ p,
+                                                             const float* __restrict__ t,
+                                                             long long numel,
+                                                             float* __restrict__ part) {
+  L3U_STAMP_SCOPE(409);
+  __shared__ float red[4];
+  float spt = 0.f, sp = 0.f, st = 0.f, se = 0.f;
+  for (long long i = blockIdx.x * 256ll + threadIdx.x; i < numel; i += (long long)gridDim.x * 256) {
+    const float pv = p[i], tv = t[i];
+    spt = fmaf(pv, tv, spt);
+    sp += pv;
+    st += tv;
+    se += bce_term(pv, tv);
+  }
+  spt = block_sum256(spt, red);
+  sp = block_sum256(sp, red);
+  st = block_sum256(st, red);
+  se = block_sum256(se, red);
+  if (threadIdx.x == 0) {
+    part[blockIdx.x * 4 + 0] = spt;
+    part[blockIdx.x * 4 + 1] = sp;
+    part[blockIdx.x * 4 + 2] = st;
+    part[blockIdx.x * 4 + 3] = se;
+  }
+}
+
+// sums[0..3] (double) = fixed-order sum of the partials
+__global__ void loss4_sums_kernel(const float* __restrict__ part, int nb, double* __restrict__ sums) {
+  L3U_STAMP_SCOPE(410);
+  double sm[4];
+  loss4_lane_sums(part, nb, sm);
+  if (threadIdx.x == 0) { sums[0] = sm[0]; sums[1] = sm[1]; sums[2] = sm[2]; sums[3] = sm[3]; }
+}
+
+__global__ void loss4_value_kernel(const double* __restrict__ sums, LossDesc fam,
+                                   float* __restrict__ loss) {
+  L3U_STAMP_SCOPE(411);
+  const Loss4Coef r = loss4_coef(sums, fam);
+  loss[0] = (float)r.loss;
+}
+
+// g_i = gscale * dL/dp_i of the family; optionally fused sigmoid backward: g_i *= p_i (1 - p_i)
+__global__ __launch_bounds__(256) void loss4_bwd_kernel(
+    const float* __restrict__ p, const float* __restrict__ t, long long numel,
+    const double* __restrict__ sums, LossDesc fam, const float* __restrict__ gscale,
+    int through_sigmoid, float* __restrict__ g) {
+  L3U_STAMP_SCOPE(412);
+  __shared__ float coef[3];
+  if (threadIdx.x == 0) {
+    const Loss4Coef r = loss4_coef(sums, fam);
+    const double s = gscale ? (double)gscale[0] : 1.0;
+    coef[0] = (float)(r.A * s);
+    coef[1] = (float)(r.B * s);
+    coef[2] = (float)(r.E * s);
+  }
+  __syncthreads();
+  const float A = coef[0], B = coef[1], E = coef[2];
+  for (long long i = blockIdx.x * 256ll + threadIdx.x; i < numel; i += (long long)gridDim.x * 256) {
+    const float tv = t[i], pv = p[i];
+    float v = loss4_grad(A - B, B, E, pv, tv);
+    if (through_sigmoid) v = v * pv * (1.f - pv);
     g[i] = v;
   }
 }
@@ -862,6 +1032,47 @@ int outconv_fwd_impl(const T* h, long long h_nstride, const float* w, const floa
   L3U_CHECK_LAUNCH();
 }
 
+L3U_INLINE_HOST bool loss_desc_ok(const LossDesc& d) {
+  return d.numel > 0.0 && (d.w_ftl != 0.0 || d.w_bce != 0.0 || d.w_dice != 0.0);
+}
+
+// l3u_outconv_fwd with the four-column partials ftl_part[N*nblocks][4]; the float4 path only for
+// 16-byte aligned h (8-byte for bf16), p and t
+template <typename T>
+int outconv_fwd_loss4_impl(const T* h, long long h_nstride, const float* w, const float* b, float* p,
+                           const float* t, float* part, int N, int C, int S, hipStream_t stream) {
+  L3U_REQUIRE(N > 0 && C > 0 && S > 0 && h && w && b && p && t && part);
+  const bool vec = S % 4 == 0 && h_nstride % 4 == 0 && C <= 32 &&
+                   (((uintptr_t)p | (uintptr_t)t) & 15) == 0 &&
+                   ((uintptr_t)h & (4 * sizeof(T) - 1)) == 0;
+  dim3 grid((S + 1023) / 1024, N);
+  if (vec) hipLaunchKernelGGL((outconv_fwd_kernel<T, true, true>), grid, dim3(256), 0, stream, h, h_nstride, w, b, p, t, part, C, S);
+  else hipLaunchKernelGGL((outconv_fwd_kernel<T, false, true>), grid, dim3(256), 0, stream, h, h_nstride, w, b, p, t, part, C, S);
+  L3U_CHECK_LAUNCH();
+}
+
+// l3u_outconv_bwd[_dz] / _ftl[_dz] for the loss family: sums[4] given, or the forward's
+// four-column partials reduced in the launch
+template <typename T>
+int outconv_bwd_loss4_impl(const float* p, const float* t, const double* sums, const float* fpart,
+                           int fnp, const LossDesc& fam, const float* gscale, const T* h,
+                           long long h_nstride, const float* w, float* dh, long long dh_nstride,
+                           double* part, float* loss, int N, int C, int S, hipStream_t stream,
+                           int dz_only) {
+  L3U_REQUIRE(N > 0 && C > 0 && C <= 32 && S > 0 && p && t && h && w && dh && part);
+  L3U_REQUIRE((sums != nullptr) != (fpart != nullptr) && (fpart == nullptr || fnp > 0));
+  L3U_REQUIRE(loss_desc_ok(fam));
+  const bool vec = S % 4 == 0 && h_nstride % 4 == 0 && dh_nstride % 4 == 0 &&
+                   (((uintptr_t)p | (uintptr_t)t | (uintptr_t)dh) & 15) == 0 &&
+                   ((uintptr_t)h & (4 * sizeof(T) - 1)) == 0;
+  dim3 grid((S + 1023) / 1024, N);
+  const size_t lds = 4 * (C + 1) * sizeof(double);
+  const float* dp = nullptr;
+  if (vec) hipLaunchKernelGGL((outconv_bwd_kernel<T, true, true>), grid, dim3(256), lds, stream, dz_only, dp, p, t, sums, 0.0, 0.0, 0.0, 0.0, gscale, h, h_nstride, w, dh, dh_nstride, part, loss, C, S, fpart, fnp, fam);
+  else hipLaunchKernelGGL((outconv_bwd_kernel<T, false, true>), grid, dim3(256), lds, stream, dz_only, dp, p, t, sums, 0.0, 0.0, 0.0, 0.0, gscale, h, h_nstride, w, dh, dh_nstride, part, loss, C, S, fpart, fnp, fam);
+  L3U_CHECK_LAUNCH();
+}
+
 template <typename T>
 int outconv_bwd_impl(const float* dp, const float* p, const float* t, const double* sums,
                      double alpha, double beta, double gamma, double smooth, const float* gscale,
@@ -876,8 +1087,8 @@ int outconv_bwd_impl(const float* dp, const float* p, const float* t, const doub
                    ((uintptr_t)h & (4 * sizeof(T) - 1)) == 0;
   dim3 grid((S + 1023) / 1024, N);
   const size_t lds = 4 * (C + 1) * sizeof(double);
-  if (vec) hipLaunchKernelGGL((outconv_bwd_kernel<T, true>), grid, dim3(256), lds, stream, dz_only, dp, p, t, sums, alpha, beta, gamma, smooth, gscale, h, h_nstride, w, dh, dh_nstride, part, loss, C, S, fpart, fnp);
-  else hipLaunchKernelGGL((outconv_bwd_kernel<T, false>), grid, dim3(256), lds, stream, dz_only, dp, p, t, sums, alpha, beta, gamma, smooth, gscale, h, h_nstride, w, dh, dh_nstride, part, loss, C, S, fpart, fnp);
+  if (vec) hipLaunchKernelGGL((outconv_bwd_kernel<T, true>), grid, dim3(256), lds, stream, dz_only, dp, p, t, sums, alpha, beta, gamma, smooth, gscale, h, h_nstride, w, dh, dh_nstride, part, loss, C, S, fpart, fnp, LossDesc());
+  else hipLaunchKernelGGL((outconv_bwd_kernel<T, false>), grid, dim3(256), lds, stream, dz_only, dp, p, t, sums, alpha, beta, gamma, smooth, gscale, h, h_nstride, w, dh, dh_nstride, part, loss, C, S, fpart, fnp, LossDesc());
   L3U_CHECK_LAUNCH();
 }
 
@@ -935,6 +1146,29 @@ L3U_TWIN(l3u_outconv_bwd_dz, P_OCB, outconv_bwd_impl(dp, p, t, sums, alpha, beta
 L3U_TWIN(l3u_outconv_bwd_ftl_dz, P_OCBF, outconv_bwd_impl((const float*)nullptr, p, t,
          (const double*)nullptr, alpha, beta, gamma, smooth, gscale, bp(h), h_nstride, w, dh, dh_nstride,
          part, loss, N, C, S, stream, ftl_part, ftl_nparts, 1))
+// the loss-family forms (descriptor scalars in place of alpha, beta, gamma, smooth)
+#define L3U_FAM_PARAMS double w_ftl, double alpha, double beta, double gamma, double smooth_ftl,      \
+    double w_bce, double global_numel, double w_dice, double smooth_dice
+#define L3U_FAM_DESC LossDesc{w_ftl, alpha, beta, gamma, smooth_ftl, w_bce, global_numel, w_dice, smooth_dice}
+L3U_TWIN(l3u_outconv_fwd_loss4, P_OCF, outconv_fwd_loss4_impl(bp(h), h_nstride, w, b, p, t, ftl_part,
+         N, C, S, stream))
+#define P_OCB4(TT) (const float* p, const float* t, const double* sums, L3U_FAM_PARAMS,              \
+    const float* gscale, const TT* h, long long h_nstride, const float* w, float* dh,                \
+    long long dh_nstride, double* part, float* loss, int N, int C, int S, hipStream_t stream)
+#define P_OCBP4(TT) (const float* p, const float* t, const float* loss_part, int loss_nparts,        \
+    L3U_FAM_PARAMS, const float* gscale, const TT* h, long long h_nstride, const float* w,            \
+    float* dh, long long dh_nstride, double* part, float* loss, int N, int C, int S,                  \
+    hipStream_t stream)
+L3U_TWIN(l3u_outconv_bwd_loss4, P_OCB4, outconv_bwd_loss4_impl(p, t, sums, (const float*)nullptr, 0,
+         L3U_FAM_DESC, gscale, bp(h), h_nstride, w, dh, dh_nstride, part, loss, N, C, S, stream, 0))
+L3U_TWIN(l3u_outconv_bwd_loss4_dz, P_OCB4, outconv_bwd_loss4_impl(p, t, sums, (const float*)nullptr,
+         0, L3U_FAM_DESC, gscale, bp(h), h_nstride, w, dh, dh_nstride, part, loss, N, C, S, stream, 1))
+L3U_TWIN(l3u_outconv_bwd_loss4p, P_OCBP4, outconv_bwd_loss4_impl(p, t, (const double*)nullptr,
+         loss_part, loss_nparts, L3U_FAM_DESC, gscale, bp(h), h_nstride, w, dh, dh_nstride, part,
+         loss, N, C, S, stream, 0))
+L3U_TWIN(l3u_outconv_bwd_loss4p_dz, P_OCBP4, outconv_bwd_loss4_impl(p, t, (const double*)nullptr,
+         loss_part, loss_nparts, L3U_FAM_DESC, gscale, bp(h), h_nstride, w, dh, dh_nstride, part,
+         loss, N, C, S, stream, 1))
 template <typename T>
 int box_copy_impl(const T* src, long long sns, int sd, int sh, int sw, T* dst, long long dns, int dd,
                   int dh, int dw, int oz, int oy, int ox, int N, int C, hipStream_t stream) {
@@ -1004,6 +1238,38 @@ int l3u_ftl_bwd(const float* p, const float* t, long long numel, const double* s
   L3U_REQUIRE(numel > 0);
   hipLaunchKernelGGL(ftl_bwd_kernel, dim3(grid_for(numel, 1024, 1024)), dim3(256), 0, stream, p, t,
                      numel, sums, alpha, beta, gamma, smooth, gscale, through_sigmoid, g);
+  L3U_CHECK_LAUNCH();
+}
+
+int l3u_loss4_reduce(const float* part, int nparts, double* sums, hipStream_t stream) {
+  L3U_REQUIRE(nparts > 0 && part && sums);
+  hipLaunchKernelGGL(loss4_sums_kernel, dim3(1), dim3(64), 0, stream, part, nparts, sums);
+  L3U_CHECK_LAUNCH();
+}
+
+int l3u_loss4_sums(const float* p, const float* t, long long numel, float* part, double* sums,
+                   hipStream_t stream) {
+  L3U_REQUIRE(numel > 0 && p && t && part && sums);
+  const int nb = grid_for(numel, 2048, 512);
+  hipLaunchKernelGGL(loss4_partials_kernel, dim3(nb), dim3(256), 0, stream, p, t, numel, part);
+  hipLaunchKernelGGL(loss4_sums_kernel, dim3(1), dim3(64), 0, stream, part, nb, sums);
+  L3U_CHECK_LAUNCH();
+}
+
+int l3u_loss4_value(const double* sums, L3U_FAM_PARAMS, float* loss, hipStream_t stream) {
+  const LossDesc fam = L3U_FAM_DESC;
+  L3U_REQUIRE(sums && loss && loss_desc_ok(fam));
+  hipLaunchKernelGGL(loss4_value_kernel, dim3(1), dim3(1), 0, stream, sums, fam, loss);
+  L3U_CHECK_LAUNCH();
+}
+
+int l3u_loss4_bwd(const float* p, const float* t, long long numel, const double* sums,
+                  L3U_FAM_PARAMS, const float* gscale, int through_sigmoid, float* g,
+                  hipStream_t stream) {
+  const LossDesc fam = L3U_FAM_DESC;
+  L3U_REQUIRE(numel > 0 && p && t && sums && g && loss_desc_ok(fam));
+  hipLaunchKernelGGL(loss4_bwd_kernel, dim3(grid_for(numel, 1024, 1024)), dim3(256), 0, stream, p, t,
+                     numel, sums, fam, gscale, through_sigmoid, g);
   L3U_CHECK_LAUNCH();
 }
 

@@ -14,6 +14,7 @@ After install():
     light_unet.models.unet3d.Lightweight3DUNet      -> l3u_amd.models.unet3d.Lightweight3DUNet
     light_unet.models.losses.FocalTverskyLoss       -> l3u_amd.models.losses.FocalTverskyLoss
     light_unet.models.losses.get_loss_function      -> l3u_amd.models.losses.get_loss_function
+    light_unet.models.losses.CombinedLoss, DiceLoss -> l3u_amd.models.losses.CombinedLoss, DiceLoss
     light_unet.models.Lightweight3DUNet / get_loss_function (package re-exports, models/__init__.py:6-8)
     light_unet.utils.sliding_window_inference_3d    -> l3u_amd.utils.sliding_window_inference_3d
 Everything else in the reference package is left untouched.
@@ -29,7 +30,7 @@ ALIAS = "l3u_amd"
 REPLACED = {
     "light_unet.utils": ("sliding_window_inference_3d",),
     "light_unet.models.unet3d": ("Lightweight3DUNet",),
-    "light_unet.models.losses": ("FocalTverskyLoss", "get_loss_function"),
+    "light_unet.models.losses": ("FocalTverskyLoss", "get_loss_function", "CombinedLoss", "DiceLoss"),
     "light_unet.models": ("Lightweight3DUNet", "FocalTverskyLoss", "get_loss_function"),
 }
 
@@ -136,6 +137,8 @@ def install(fast_step=False, lesion=True, device_patches=False):
         "Lightweight3DUNet": sys.modules[ALIAS + ".models.unet3d"].Lightweight3DUNet,
         "FocalTverskyLoss": sys.modules[ALIAS + ".models.losses"].FocalTverskyLoss,
         "get_loss_function": sys.modules[ALIAS + ".models.losses"].get_loss_function,
+        "CombinedLoss": sys.modules[ALIAS + ".models.losses"].CombinedLoss,
+        "DiceLoss": sys.modules[ALIAS + ".models.losses"].DiceLoss,
         "sliding_window_inference_3d": sys.modules[ALIAS + ".utils"].sliding_window_inference_3d,
     }
     mods = {}

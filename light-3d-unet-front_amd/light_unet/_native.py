@@ -23,6 +23,10 @@ F = ctypes.c_float
 D = ctypes.c_double
 U64 = ctypes.c_ulonglong
 
+# the loss-family descriptor of the l3u_*loss4* entry points (include/l3u.h): w_ftl, alpha, beta,
+# gamma, smooth_ftl, w_bce, numel, w_dice, smooth_dice
+_FAM = [D] * 9
+
 # name -> argtypes (stream is always the trailing void*; every function returns int hipError_t)
 _SIGS = {
     "l3u_abi_version": [],
@@ -101,6 +105,16 @@ _SIGS = {
     "l3u_dw3_bwd_rank1": [I, I, I, I, I],
     "l3u_dwpw_stat_nsb": [I, I, I, I, I],
     "l3u_dwpw_fwd": [P, L, P, P, P, P, P, L, P, P, P, L, P, P, L, I, I, I, I, I, I, P],
+    # the loss family (FocalTversky / Combined / Dice) on four sums; _FAM: the nine descriptor scalars
+    "l3u_loss4_sums": [P, P, L, P, P, P],
+    "l3u_loss4_reduce": [P, I, P, P],
+    "l3u_loss4_value": [P] + _FAM + [P, P],
+    "l3u_loss4_bwd": [P, P, L, P] + _FAM + [P, I, P, P],
+    "l3u_outconv_fwd_loss4": [P, L, P, P, P, P, P, I, I, I, P],
+    "l3u_outconv_bwd_loss4": [P, P, P] + _FAM + [P, P, L, P, P, L, P, P, I, I, I, P],
+    "l3u_outconv_bwd_loss4_dz": [P, P, P] + _FAM + [P, P, L, P, P, L, P, P, I, I, I, P],
+    "l3u_outconv_bwd_loss4p": [P, P, P, I] + _FAM + [P, P, L, P, P, L, P, P, I, I, I, P],
+    "l3u_outconv_bwd_loss4p_dz": [P, P, P, I] + _FAM + [P, P, L, P, P, L, P, P, I, I, I, P],
 }
 # entry points with a _bf16 twin (same arguments; saved activations stored as bf16, gradients
 # fp32, include/l3u.h)
@@ -112,7 +126,9 @@ BF16_TWINS = ("l3u_dw3_fwd", "l3u_dw3_bwd", "l3u_pw_fwd", "l3u_pw_fwd2", "l3u_pw
               "l3u_outconv_bwd_ftl", "l3u_box_copy",
               "l3u_front_fwd", "l3u_dwpw_fwd", "l3u_outconv_bwd_dz", "l3u_outconv_bwd_ftl_dz",
               "l3u_norm_act_bwd_reduce_r1", "l3u_pw_bwd_tail_r1", "l3u_norm_act_bwd_reduce_up",
-              "l3u_pw_bwd_tail_up", "l3u_norm_act_bwd_up")
+              "l3u_pw_bwd_tail_up", "l3u_norm_act_bwd_up", "l3u_outconv_fwd_loss4",
+              "l3u_outconv_bwd_loss4", "l3u_outconv_bwd_loss4_dz", "l3u_outconv_bwd_loss4p",
+              "l3u_outconv_bwd_loss4p_dz")
 for _n in BF16_TWINS:
     _SIGS[_n + "_bf16"] = _SIGS[_n]
 # query helpers that return a value instead of an error code

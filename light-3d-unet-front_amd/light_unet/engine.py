@@ -355,10 +355,11 @@ class UNetEngine:
 
     # ------------------------------------------------------------------ forward
     def forward(self, flat, x, training=False, dropout_p=0.0, counter=None, save=True, target=None,
-                ftl_part=None, bump_counter=True):
+                ftl_part=None, bump_counter=True, loss4=False):
         """x: [N,1,D,H,W] fp32 on device -> probabilities [N,1,D,H,W] (+ saved state).  With a
         target (same shape) the out_conv launch also writes the FocalTversky partials into
-        ftl_part [N * l3u_outconv_nblocks(S)][3]."""
+        ftl_part [N * l3u_outconv_nblocks(S)][3]; loss4: the loss family's four-column partials
+        [..][4] (l3u_outconv_fwd_loss4: CombinedLoss / DiceLoss)."""
         self.check_shape(x)
         x = x.contiguous()
         if x.dtype != torch.float32:
@@ -371,17 +372,17 @@ class UNetEngine:
             self.fwd_arena.reset(None)
             try:
                 self._forward_impl(flat, x, training, dropout_p, counter, save, dev, target, ftl_part,
-                                   bump_counter)
+                                   bump_counter, loss4)
             finally:
                 self._dry = False
             self._arenas[key] = torch.empty(max(self.fwd_arena.top, 64), dtype=torch.float32,
                                             device=dev)
         self.fwd_arena.reset(self._arenas[key])
         return self._forward_impl(flat, x, training, dropout_p, counter, save, dev, target, ftl_part,
-                                  bump_counter)
+                                  bump_counter, loss4)
 
     def _forward_impl(self, flat, x, training, dropout_p, counter, save, dev, target=None,
-                      ftl_part=None, bump_counter=True):
+                      ftl_part=None, bump_counter=True, loss4=False):
         N, _, D, H, W = x.shape
         c0, c1, c2, c3 = self.enc
         dims = [(D >> k, H >> k, W >> k) for k in range(4)]
@@ -459,7 +460,10 @@ class UNetEngine:
         sv["ups"] = ups
         p = self._f32(N, 1, D, H, W, device=dev)   # probabilities stay fp32 (the loss input)
         # with a target, the FocalTversky first-stage partials come out of the same launch
-        self._call("l3u_outconv_fwd", prev.p, prev.ns, self._w(flat, "out_conv.weight"),
+        if loss4 and target is None:
+            raise ValueError("loss4 partials need a target")
+        self._call("l3u_outconv_fwd_loss4" if loss4 else "l3u_outconv_fwd", prev.p, prev.ns,
+                   self._w(flat, "out_conv.weight"),
                    self._w(flat, "out_conv.bias"), p.data_ptr(),
                    target.data_ptr() if target is not None else None,
                    ftl_part.data_ptr() if target is not None else None, N, c0, S[0], st)
@@ -692,7 +696,7 @@ class UNetEngine:
         return sv
 
     # ------------------------------------------------------------------ backward
-    def backward(self, flat, gflat, sv, dp, need_dx=False, ftl=None, opt=None):
+    def backward(self, flat, gflat, sv, dp, need_dx=False, ftl=None, opt=None, family=None):
         """Given dL/dp write all parameter gradients into gflat (overwrite) and return dL/dx if
         need_dx.  opt: the FlatAdamW over (flat, gflat) of a one-process step; when the gradient
         reduction covers every parameter once, its launch also applies the update and
@@ -700,7 +704,11 @@ class UNetEngine:
         (alpha, beta, gamma, smooth)[, loss tensor[, partials, n_partials]]); its gradient is
         formed inside the out_conv backward, which also writes the loss value when a loss tensor
         is given.  sums = None: the out_conv backward reduces the forward's FocalTversky
-        partials itself (l3u_outconv_bwd_ftl; no reduce launch)."""
+        partials itself (l3u_outconv_bwd_ftl; no reduce launch).
+        family: the nine loss-family descriptor scalars (losses.family_descriptor) for
+        CombinedLoss / DiceLoss; `ftl` then holds (target, sums [4] or None, None, loss tensor[,
+        four-column partials, n_partials]) and the l3u_outconv_bwd_loss4* forms run.  family =
+        None issues exactly the FocalTversky calls."""
         N = sv["N"]
         D, H, W = sv["dims"][0]
         self.set_act_dtype(sv["adt"])
@@ -713,7 +721,7 @@ class UNetEngine:
                 self._items_rec = []
                 self.seg_bytes = {}
                 try:
-                    self._backward_impl(flat, gflat, sv, dp, need_dx, ftl)
+                    self._backward_impl(flat, gflat, sv, dp, need_dx, ftl, family)
                 finally:
                     self._dry = False
                 dev = sv["p"].device
@@ -727,7 +735,7 @@ class UNetEngine:
                 self._cover_once[key] = _items_cover_once(self._items_rec, gflat.numel())
             self.bwd_arena.reset(self._arenas[key])
             self._items_rec = []
-            dx = self._backward_impl(flat, gflat, sv, dp, need_dx, ftl)
+            dx = self._backward_impl(flat, gflat, sv, dp, need_dx, ftl, family)
         finally:
             self._grad_phase = False
         items = self._items[key]
@@ -741,7 +749,7 @@ class UNetEngine:
                      items.shape[0], gflat.data_ptr(), nat.stream())
         return dx
 
-    def _backward_impl(self, flat, gflat, sv, dp, need_dx, ftl=None):
+    def _backward_impl(self, flat, gflat, sv, dp, need_dx, ftl=None, family=None):
         N = sv["N"]
         dims, S = sv["dims"], sv["S"]
         c0, c1, c2, c3 = self.enc
@@ -766,6 +774,18 @@ class UNetEngine:
             self._call("l3u_outconv_bwd" + sfx, g[0], sv["p"].data_ptr(), *g[1:], h.p, h.ns,
                        self._w(flat, "out_conv.weight"), dh.data_ptr(), dhns, A.ptr(po),
                        loss_ptr, N, c0, S[0], st)
+        elif family is not None:   # the loss family's gradient from the four global sums
+            t, sums = ftl[:2]
+            if len(ftl) > 3 and ftl[3] is not None:
+                loss_ptr = ftl[3].data_ptr()
+            tail = (None, h.p, h.ns, self._w(flat, "out_conv.weight"), dh.data_ptr(), dhns,
+                    A.ptr(po), loss_ptr, N, c0, S[0], st)
+            if sums is None:   # reduced inside the launch from the forward's partials
+                self._call("l3u_outconv_bwd_loss4p" + sfx, sv["p"].data_ptr(), t.data_ptr(),
+                           ftl[4].data_ptr(), ftl[5], *family, *tail)
+            else:
+                self._call("l3u_outconv_bwd_loss4" + sfx, sv["p"].data_ptr(), t.data_ptr(),
+                           sums.data_ptr(), *family, *tail)
         else:   # FocalTversky gradient formed inside the kernel from the global sums
             t, sums, (alpha, beta, gamma, smooth) = ftl[:3]
             if len(ftl) > 3 and ftl[3] is not None:   # the loss value, written by the same launch

@@ -8,7 +8,7 @@ trainer.py:208-258 / :260-347).  They keep the reference loops' meaning:
     step-based mode runs every FL batch, then round(fl_batches * dlbcl_steps_ratio) DLBCL steps
     (or `dlbcl_steps`), re-iterating the DLBCL loader when it runs out, trainer.py:262-269,
     :301-312);
-  * the same update: forward -> FocalTversky -> backward -> AdamW(lr, weight_decay, betas, eps of
+  * the same update: forward -> criterion -> backward -> AdamW(lr, weight_decay, betas, eps of
     the Trainer's torch optimizer), with the learning rate read from that optimizer at the start
     of every epoch, so the Trainer's CosineAnnealingLR / ReduceLROnPlateau steps (trainer.py:
     532-542) drive it;
@@ -26,12 +26,13 @@ batch) runs the same step eagerly.
 The torch optimizer is not stepped; its per-parameter state is kept as views of the flat AdamW
 state (exp_avg / exp_avg_sq, and `step`), refreshed at the end of every epoch, so
 `optimizer.state_dict()` in the Trainer's checkpoints (trainer.py:447-470) holds the real
-moments.  Losses other than FocalTversky (CombinedLoss, DiceLoss: not enabled by any shipped
-config) fall back to the reference loop.
+moments.  The criterion may be FocalTverskyLoss, CombinedLoss (`use_combined_loss`) or DiceLoss
+(exact types, no reduce_hook): all three run inside the out_conv launches of the step.  Any
+other criterion falls back to the reference loop.
 """
 import torch
 
-from .models.losses import FocalTverskyLoss
+from .models.losses import CombinedLoss, DiceLoss, FocalTverskyLoss
 from .train_step import TrainStep
 
 _FALLBACK = "_l3u_reference_loops"
@@ -45,10 +46,10 @@ class FastLoop:
         model, opt = trainer.model, trainer.optimizer
         crit = trainer.criterion
         pg = opt.param_groups[0]
-        self.step = TrainStep(model, {"alpha": crit.alpha, "beta": crit.beta, "gamma": crit.gamma,
-                                      "smooth": crit.smooth},
-                              lr=pg["lr"], weight_decay=pg["weight_decay"], betas=pg["betas"],
-                              eps=pg["eps"], group=group, ftl_mode=ftl_mode)
+        # the criterion itself: FocalTversky keeps its entry points, CombinedLoss / DiceLoss run
+        # as the loss family in the same launches (train_step.parse_loss)
+        self.step = TrainStep(model, crit, lr=pg["lr"], weight_decay=pg["weight_decay"],
+                              betas=pg["betas"], eps=pg["eps"], group=group, ftl_mode=ftl_mode)
         if self.step.world > 1:   # identical initial weights on every rank (DDP semantics)
             import torch.distributed as dist
             dist.broadcast(self.step.flat, 0, group=group)
@@ -137,7 +138,8 @@ def _loop(self):
 
 
 def _usable(self):
-    return type(self.criterion) is FocalTverskyLoss and getattr(self.criterion, "reduce_hook", None) is None
+    return type(self.criterion) in (FocalTverskyLoss, CombinedLoss, DiceLoss) and \
+        getattr(self.criterion, "reduce_hook", None) is None
 
 
 def _tqdm(it, **kw):

@@ -10,6 +10,11 @@ the math needs it:
     every rank computes the loss of the GLOBAL batch (losses.py:40-46 semantics); gradients are
     then all-reduced with SUM (the global loss is one function of all ranks' voxels);
   * local mode: each rank's own loss, gradients averaged (plain DDP).
+The loss is the reference's loss config (losses.py:116-147): FocalTverskyLoss, or, on the same
+launches with one more partial column and one more gradient term, CombinedLoss
+(`use_combined_loss`, the reference's fallback for unstable training) and DiceLoss.  For those the
+four sums {sum p*t, sum p, sum t, sum bce} are exchanged in one call and the BCE mean divides by
+world * local element count: exact mode needs equal shapes on all ranks.
 Both collectives are RCCL over xGMI (torch.distributed backend "nccl") on one flat buffer each:
 24 B and 0.87 MB (3.25 MB for the 32->256 model) per step.
 """
@@ -20,7 +25,34 @@ import torch.distributed as dist
 
 from . import _native as nat
 from .exchange import check_mode, exchange_ftl_sums, exchange_grads, world_size
+from .models.losses import FocalTverskyLoss, family_descriptor, loss_family
 from .optim import FlatAdamW
+
+
+def parse_loss(loss_cfg):
+    """(FocalTversky (alpha, beta, gamma, smooth), None) or (None, family descriptor with numel 1)
+    from the reference's loss config dict (name, use_combined_loss, combined_loss_weights,
+    alpha/beta/gamma; losses.py:116-147) or from a criterion instance."""
+    if isinstance(loss_cfg, torch.nn.Module):
+        if type(loss_cfg) is FocalTverskyLoss:
+            c = loss_cfg
+            return (float(c.alpha), float(c.beta), float(c.gamma), float(c.smooth)), None
+        return None, loss_family(loss_cfg)
+    cfg = loss_cfg or {}
+    abg = (float(cfg.get("alpha", 0.7)), float(cfg.get("beta", 0.3)), float(cfg.get("gamma", 0.75)))
+    if cfg.get("use_combined_loss", False):
+        w = cfg.get("combined_loss_weights", {"focal_tversky": 0.8, "bce": 0.2})
+        wf, wb = float(w["focal_tversky"]), float(w["bce"])
+        assert abs(wf + wb - 1.0) < 1e-6, f"Weights must sum to 1.0, got {wf + wb}"
+        assert abs(abg[0] + abg[1] - 1.0) < 1e-6
+        return None, family_descriptor(wf, *abg, 1e-6, w_bce=wb)
+    name = cfg.get("name", "FocalTverskyLoss")
+    if name == "FocalTverskyLoss":
+        assert abs(abg[0] + abg[1] - 1.0) < 1e-6
+        return abg + (float(cfg.get("smooth", 1e-6)),), None
+    if name == "DiceLoss":
+        return None, family_descriptor(w_dice=1.0, smooth_dice=float(cfg.get("smooth", 1e-6)))
+    raise ValueError(f"Unknown loss function: {name}")
 
 
 def _rccl(group):
@@ -32,7 +64,10 @@ class TrainStep:
     def __init__(self, model, loss_cfg=None, lr=1e-4, weight_decay=1e-5, betas=(0.9, 0.999),
                  eps=1e-8, group=None, ftl_mode="exact", distributed=True, dtype=None,
                  force_exchange=False, capture_collectives=None):
-        """dtype: activation storage of the step (torch.float32 or torch.bfloat16; default the
+        """loss_cfg: the reference's loss config dict (see parse_loss) or a FocalTverskyLoss /
+        CombinedLoss / DiceLoss instance; unknown names raise ValueError, combined weights not
+        summing to 1 AssertionError.
+        dtype: activation storage of the step (torch.float32 or torch.bfloat16; default the
         model's compute_dtype, else fp32).  Master weights, AdamW state, gradients and the loss
         stay fp32.
         force_exchange: run the data-parallel step (FocalTversky sums and gradient all-reduces,
@@ -45,12 +80,10 @@ class TrainStep:
         captured replay has been recorded yet, so the eager segments stay the default there);
         L3U_EAGER_COLLECTIVES=1 forces the segments everywhere.  gloo collectives run on the
         host and always stay eager."""
-        loss_cfg = loss_cfg or {}
-        self.alpha = float(loss_cfg.get("alpha", 0.7))
-        self.beta = float(loss_cfg.get("beta", 0.3))
-        self.gamma = float(loss_cfg.get("gamma", 0.75))
-        self.smooth = float(loss_cfg.get("smooth", 1e-6))
-        assert abs(self.alpha + self.beta - 1.0) < 1e-6
+        abgs, self.family = parse_loss(loss_cfg)
+        if abgs is None:   # the family's FocalTversky term
+            abgs = self.family[1:5]
+        self.alpha, self.beta, self.gamma, self.smooth = abgs
         check_mode(ftl_mode)
         self.model = model
         self.engine = model.engine
@@ -82,31 +115,40 @@ class TrainStep:
         # the out_conv launch also produces the FocalTversky partials (losses.py:40-42)
         N, S = x.shape[0], x[0].numel()
         nparts = N * nat.query("l3u_outconv_nblocks", S)
-        part = torch.empty(nparts * 3, dtype=torch.float32, device=x.device)
+        fam = self.family is not None
+        ncol = 4 if fam else 3
+        part = torch.empty(nparts * ncol, dtype=torch.float32, device=x.device)
         self.engine.set_act_dtype(self.act_dtype)
         p, sv = self.engine.forward(self.flat, x, training=self.model.training,
                                     dropout_p=self.model.dropout_p,
                                     counter=self.model._rng_counter, bump_counter=False,
                                     save=True, target=t,
-                                    ftl_part=part)
+                                    ftl_part=part, loss4=fam)
         if not self.exchange:
             # one process: the out_conv backward reduces the partials itself (no reduce launch)
             return p, sv, (part, nparts)
-        sums = torch.empty(3, dtype=torch.float64, device=p.device)
-        nat.call("l3u_ftl_reduce", part.data_ptr(), nparts, sums.data_ptr(), nat.stream())
+        sums = torch.empty(ncol, dtype=torch.float64, device=p.device)
+        nat.call("l3u_loss4_reduce" if fam else "l3u_ftl_reduce", part.data_ptr(), nparts,
+                 sums.data_ptr(), nat.stream())
         return p, sv, sums
 
     def _bwd(self, p, sv, t, sums):
         # dL/dp is formed inside the out_conv backward from t and the (global) sums; the same
         # launch writes the loss value (losses.py:52-54)
         abgs = (self.alpha, self.beta, self.gamma, self.smooth)
+        family = None
+        if self.family is not None:
+            # the BCE mean runs over the elements the sums cover: all ranks' (equal) shards in
+            # exact mode, this rank's own in local mode
+            glob = self.world if self.exchange and self.ftl_mode == "exact" else 1
+            family = self.family[:6] + (float(p.numel() * glob),) + self.family[7:]
         if isinstance(sums, tuple):   # (partials, count): reduced inside the out_conv backward
             ftl = (t, None, abgs, self.loss, sums[0], sums[1])
         else:
             ftl = (t, sums, abgs, self.loss)
         # one process: the gradient reduction launch also applies the AdamW update
         self.engine.backward(self.flat, self.gflat, sv, None, need_dx=False, ftl=ftl,
-                             opt=None if self.exchange else self.opt)
+                             opt=None if self.exchange else self.opt, family=family)
         return self.engine.applied_update
 
     def _grad_exchange(self):
