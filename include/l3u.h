@@ -427,6 +427,37 @@ int l3u_ccl_label_b(const float* src, float threshold, int* parent, int* label, 
 int l3u_ccl_stats_b(int* label, const int* remap, const float* prob, unsigned long long* stats,
                     int ncomp, int B, int D, int H, int W, int lead4, hipStream_t stream);
 
+/* The threshold sweep (Trainer.validate's threshold_sensitivity_range, trainer.py:423-439): all K
+ * binarisations of one probability map in one launch sequence.
+ * l3u_thr_levels: p = prob (* mask when given: one fp32 multiply, numpy's float32 product);
+ * level[v] = number of k with p[v] >= thr[k] (thr[K] strictly ascending, 1 <= K <= 32; the same
+ * fp32 >= as l3u_ccl_label; NaN compares false everywhere), so the foreground at thr[k] is
+ * level >= k + 1.  hist[(K + 1) * 2] uint64 (zeroed here): voxels per (level, target >= 0.5),
+ * target optional (column 1 stays 0).  masked (optional) receives p.
+ * l3u_ccl_label_lv: labels the K binarisations level >= k0 + k + 1, k = 0..K-1 (k0 + K <= 32), of
+ * one [D, H, W] volume, each exactly as l3u_ccl_label labels it.  The levels are independent
+ * volumes with level-local parent indices (D*H*W < 2^31 whatever K): parent[K*n], label[K*n]
+ * int32, chunk_count[K * (l3u_ccl_nchunks(n) + 1)] int32 with each level's component count in the
+ * last slot of its row, and offs[K + 1] int32 = exclusive prefix sums of those counts.
+ * l3u_ccl_stats_lv: l3u_ccl_stats for all K levels; component l of level k is row
+ * offs[k] + l - 1 of stats[total * 12], total = offs[K] > 0.
+ * l3u_ccl_pairs_lv: l3u_ccl_pairs of every level against ONE labelling label_b[n] with nb
+ * components; level k's (num_k + 1) x (nb + 1) table starts at (offs[k] + k) * (nb + 1) of
+ * inter[(offs[K] + K) * (nb + 1)] (zeroed by the caller).
+ * l3u_ccl_lv_max_levels: how many levels' workspaces (parent, label, chunk_count) fit into
+ * max_bytes for an n-voxel volume, clamped to 1..32 (pure host). */
+int l3u_ccl_lv_max_levels(long long n, long long max_bytes);
+int l3u_thr_levels(const float* prob, const float* mask, const float* target, const float* thr,
+                   int K, unsigned char* level, unsigned long long* hist, float* masked,
+                   long long n, hipStream_t stream);
+int l3u_ccl_label_lv(const unsigned char* level, int k0, int K, int* parent, int* label,
+                     int* chunk_count, int* offs, int D, int H, int W, hipStream_t stream);
+int l3u_ccl_stats_lv(const int* label, const float* prob, const int* offs,
+                     unsigned long long* stats, int total, int K, int D, int H, int W,
+                     hipStream_t stream);
+int l3u_ccl_pairs_lv(const int* label_lv, const int* label_b, int nb, const int* offs,
+                     unsigned int* inter, int K, long long n, hipStream_t stream);
+
 /* ---- UpBlock pad / crop (light_unet/models/unet3d.py:130-138) -----------------------------
  * dst[n][c][z][y][x] = src[n][c][z-oz][y-oy][x-ox] inside src's (sd, sh, sw) box, 0 elsewhere,
  * over the whole (dd, dh, dw) dst box.  Forward: the ConvTranspose3d output padded to the skip

@@ -112,7 +112,7 @@ def _bind_device_patches(done):
     done["light_unet.datasets.loader"] = ["_create_train_loader"]
 
 
-def install(fast_step=False, lesion=True, device_patches=False):
+def install(fast_step=False, lesion=True, device_patches=False, fast_validate=False):
     """Bind this build's model and loss into the already-importable reference package.
     Returns {module: [names]} of what was replaced.  Raises ImportError when the reference's
     light_unet.models.{unet3d,losses} cannot be imported (nothing is half-installed).
@@ -129,10 +129,18 @@ def install(fast_step=False, lesion=True, device_patches=False):
     device_patches=True also makes get_data_loader's training loaders cut
     and augment their patches on the device (light_unet/patches.py; num_workers = 0 draw
     semantics, DevicePatchLoader), so the graph-replayed step never waits on host workers or a
-    PCIe copy.  Needs light_unet.datasets.loader (and its NIfTI reader)."""
+    PCIe copy.  Needs light_unet.datasets.loader (and its NIfTI reader).
+
+    fast_validate=True also replaces Trainer.validate (trainer.py:349-445) with
+    light_unet/fast_trainer.py's: probability maps stay on the device from the sliding window to
+    the metrics, the captured network forward is reused across cases and epochs, and every
+    threshold of threshold_sensitivity_range is evaluated from one level-batched labelling per
+    case (lesion.sweep_metrics).  Same return value; the original stays reachable as
+    Trainer._l3u_reference_validate.  Needs light_unet.core.trainer."""
 
     amd = load()
-    trainer_mod = importlib.import_module("light_unet.core.trainer") if fast_step else None
+    trainer_mod = (importlib.import_module("light_unet.core.trainer")
+                   if (fast_step or fast_validate) else None)
     src = {
         "Lightweight3DUNet": sys.modules[ALIAS + ".models.unet3d"].Lightweight3DUNet,
         "FocalTverskyLoss": sys.modules[ALIAS + ".models.losses"].FocalTverskyLoss,
@@ -156,6 +164,10 @@ def install(fast_step=False, lesion=True, device_patches=False):
         fast = importlib.import_module(ALIAS + ".fast_trainer")
         fast.bind(trainer_mod.Trainer)
         done["light_unet.core.trainer"] = ["Trainer.train_epoch", "Trainer._train_epoch_step_based"]
+    if fast_validate:
+        fast = importlib.import_module(ALIAS + ".fast_trainer")
+        fast.bind_validate(trainer_mod.Trainer)
+        done.setdefault("light_unet.core.trainer", []).append("Trainer.validate")
     if device_patches:
         _bind_device_patches(done)
     if lesion:

@@ -20,6 +20,8 @@ its result is broadcast, so every rank takes the same model-selection, scheduler
 early-stopping decisions (trainer.py:505-541) and the ranks' collectives stay in step.  Only
 rank 0 writes checkpoints (the weights are identical on every rank after each step's gradient
 all-reduce).  Unlike scripts/train.py:55 the config file is never rewritten.
+`--fast-validate` runs that rank-0 validation on device-resident probability maps
+(l3u_plugin.install(fast_validate=True): cached forward graph, one threshold sweep per case).
 """
 import argparse
 import os
@@ -63,6 +65,9 @@ def main(argv=None):
     ap.add_argument("--device-patches", action="store_true",
                     help="cut and augment training patches on the device (l3u_amd.patches; "
                          "num_workers = 0 draw semantics, per-rank RNG streams)")
+    ap.add_argument("--fast-validate", action="store_true",
+                    help="device-resident validation: cached forward graph and one threshold "
+                         "sweep per case (l3u_amd.fast_trainer.validate)")
     a = ap.parse_args(argv)
 
     import torch
@@ -80,7 +85,8 @@ def main(argv=None):
     if _HERE not in sys.path:
         sys.path.insert(0, _HERE)
     import l3u_plugin
-    l3u_plugin.install(fast_step=True, device_patches=a.device_patches)
+    l3u_plugin.install(fast_step=True, device_patches=a.device_patches,
+                       fast_validate=a.fast_validate)
     from light_unet.core.config import ConfigManager
     from light_unet.core.trainer import Trainer
 

@@ -93,6 +93,12 @@ _SIGS = {
     "l3u_ccl_pairs": [P, P, I, P, L, P],
     "l3u_ccl_label_b": [P, F, P, P, P, I, I, I, I, P],
     "l3u_ccl_stats_b": [P, P, P, P, I, I, I, I, I, I, P],
+    # the threshold sweep: level encoding + level-batched labelling / stats / overlaps
+    "l3u_ccl_lv_max_levels": [L, L],
+    "l3u_thr_levels": [P, P, P, P, I, P, P, P, L, P],
+    "l3u_ccl_label_lv": [P, I, I, P, P, P, P, I, I, I, P],
+    "l3u_ccl_stats_lv": [P, P, P, P, I, I, I, I, I, P],
+    "l3u_ccl_pairs_lv": [P, P, I, P, P, I, L, P],
     "l3u_cast_bf16_f32": [P, P, L, P],
     "l3u_outconv_bwd_dz": [P, P, P, P, D, D, D, D, P, P, L, P, P, L, P, P, I, I, I, P],
     "l3u_outconv_bwd_ftl_dz": [P, P, P, I, D, D, D, D, P, P, L, P, P, L, P, P, I, I, I, P],
@@ -137,7 +143,8 @@ _QUERIES = {"l3u_abi_version", "l3u_dw3_nchunk", "l3u_pw_stat_nsb", "l3u_pw_bwd_
             "l3u_norm_act_nblocks", "l3u_outconv_nblocks", "l3u_ftl_nblocks",
             "l3u_gconv3_nblocks", "l3u_gconv3_wgrad_nparts", "l3u_front_nblocks",
             "l3u_ccl_nchunks", "l3u_dwpw_supported", "l3u_dwpw_stat_nsb",
-            "l3u_dw3_bwd_rank1", "l3u_pw_bwd2_supported", "l3u_pw_bwd_chunk"}
+            "l3u_dw3_bwd_rank1", "l3u_pw_bwd2_supported", "l3u_pw_bwd_chunk",
+            "l3u_ccl_lv_max_levels"}
 
 _lib = None
 

@@ -29,13 +29,25 @@ state (exp_avg / exp_avg_sq, and `step`), refreshed at the end of every epoch, s
 moments.  The criterion may be FocalTverskyLoss, CombinedLoss (`use_combined_loss`) or DiceLoss
 (exact types, no reduce_hook): all three run inside the out_conv launches of the step.  Any
 other criterion falls back to the reference loop.
+
+`l3u_plugin.install(fast_validate=True)` binds `validate` below as `Trainer.validate`
+(trainer.py:349-445): the same cases, masks, spacings, thresholds, `_is_better_metric` calls and
+return value, but the probability maps stay on the device from the sliding window to the metrics
+(`sliding_window_inference_3d(output="device", forward_cache=...)`), and all thresholds of
+`threshold_sensitivity_range` are evaluated by one `lesion.sweep_metrics` call: one level
+encoding and one level-batched labelling per case instead of an upload and two labellings per
+case and threshold.  The captured network forward and the targets' labellings are kept per
+Trainer, so later epochs neither capture nor label the targets again.
 """
 import torch
 
+from . import lesion
 from .models.losses import CombinedLoss, DiceLoss, FocalTverskyLoss
 from .train_step import TrainStep
+from .utils import sliding_window_inference_3d
 
 _FALLBACK = "_l3u_reference_loops"
+_FALLBACK_VALIDATE = "_l3u_reference_validate"
 
 
 class FastLoop:
@@ -241,4 +253,115 @@ def bind(trainer_cls):
                                              trainer_cls._train_epoch_step_based})
     trainer_cls.train_epoch = train_epoch
     trainer_cls._train_epoch_step_based = train_epoch_step_based
+    return trainer_cls
+
+
+# ---------------------------------------------------------------------- validation
+def evaluate_maps(prob_maps, labels, spacings, thresholds, tie_threshold, is_better,
+                  body_masks=None, target_cache=None, case_keys=None):
+    """The post-inference stage of Trainer.validate (trainer.py:423-445) on probability maps
+    (numpy or device): the metrics at every threshold from one lesion.sweep_metrics call, then the
+    reference's selection loop with `is_better` (the Trainer's _is_better_metric).  Returns the
+    chosen metrics dict with best_threshold / best_recall / best_dsc_macro."""
+    thresholds = list(thresholds)
+    swept = lesion.sweep_metrics(prob_maps, labels, thresholds, spacing=spacings,
+                                 body_masks=body_masks, target_cache=target_cache,
+                                 case_keys=case_keys)
+    best_threshold, best_metrics = thresholds[0], swept[0]
+    best_recall = best_metrics["lesion_wise_recall"]
+    best_dsc_macro = best_metrics["voxel_wise_dsc_macro"]
+    for threshold, metrics in zip(thresholds[1:], swept[1:]):
+        better, _ = is_better(metrics["lesion_wise_recall"], metrics["voxel_wise_dsc_macro"],
+                              best_recall, best_dsc_macro, tie_threshold)
+        if better:
+            best_recall = metrics["lesion_wise_recall"]
+            best_dsc_macro = metrics["voxel_wise_dsc_macro"]
+            best_threshold = threshold
+            best_metrics = metrics
+    best_metrics["best_threshold"] = best_threshold
+    best_metrics["best_recall"] = best_recall
+    best_metrics["best_dsc_macro"] = best_dsc_macro
+    return best_metrics
+
+
+def _case_id(case_ids, b):
+    """The batch's b-th case id as a hashable key, or None where the loader gives none."""
+    try:
+        cid = case_ids[b]
+    except (TypeError, IndexError, KeyError):
+        return None
+    if isinstance(cid, torch.Tensor):
+        cid = cid.tolist()
+    if isinstance(cid, list):
+        cid = tuple(cid)
+    try:
+        hash(cid)
+    except TypeError:
+        return None
+    return cid
+
+
+def validate(self, epoch):
+    """Trainer.validate (trainer.py:349-445) with device-resident probability maps."""
+    self.model.eval()
+    state = getattr(self, "_l3u_validate", None)
+    if state is None:
+        state = self._l3u_validate = {"forward": {}, "targets": {}}
+    maps, all_labels, all_spacings, masks, keys = [], [], [], [], []
+    target_spacing = self._get_target_spacing()
+    default_threshold = self.config["validation"]["default_threshold"]
+    patch_size = tuple(self.config["data"]["patch_size"])
+    bm = self.config.get("data", {}).get("body_mask", {})
+    apply_body_mask = bm.get("apply_to_validation", False) and bm.get("enabled", False)
+    dev = torch.device(self.device)
+    with torch.no_grad():
+        for batch in _tqdm(self.val_loader, desc=f"Epoch {epoch+1} [Val]"):
+            case_ids = spacings = body_masks = None
+            if isinstance(batch, (list, tuple)) and len(batch) >= 5:
+                images, labels, case_ids, spacings, body_masks = batch[:5]
+            elif isinstance(batch, (list, tuple)) and len(batch) >= 4:
+                images, labels, case_ids, spacings = batch[:4]
+            else:
+                images, labels = batch[0], batch[1]
+            if images.ndim not in (4, 5):
+                raise ValueError(f"Unexpected image shape: {images.shape}")
+            for b in range(images.shape[0]):
+                pick = (lambda t: t[b, 0]) if images.ndim == 5 else (lambda t: t[b])
+                image = pick(images).to(device=dev, dtype=torch.float32)
+                prob = sliding_window_inference_3d(image=image, model=self.model,
+                                                   patch_size=patch_size, overlap=0.5, device=dev,
+                                                   use_gaussian=True, output="device",
+                                                   forward_cache=state["forward"])
+                mask = pick(body_masks) if (apply_body_mask and body_masks is not None) else None
+                # numpy's prob_map * body_mask with the mask's own dtype (a host tensor becomes the
+                # numpy array the reference multiplies by)
+                masks.append(mask.cpu().numpy() if isinstance(mask, torch.Tensor) and not mask.is_cuda
+                             else mask)
+                maps.append(prob)
+                all_labels.append(pick(labels).cpu().numpy())
+                all_spacings.append(self._resolve_spacing_value(spacings, b, target_spacing)
+                                    if spacings is not None else target_spacing)
+                cid = _case_id(case_ids, b) if case_ids is not None else None
+                keys.append(("pos", len(keys)) if cid is None else ("id", cid))
+    if len(maps) == 0:
+        return 0.0, {"lesion_wise_recall": 0.0, "lesion_wise_precision": 0.0,
+                     "voxel_wise_dsc_macro": 0.0, "voxel_wise_dsc_micro": 0.0,
+                     "fp_per_case": 0.0, "best_threshold": default_threshold,
+                     "best_recall": 0.0, "best_dsc_macro": 0.0}
+    if len(set(keys)) != len(keys):   # repeated ids: positions are the only safe keys
+        keys = [("pos", i) for i in range(len(keys))]
+    thresholds = self.config["validation"].get("threshold_sensitivity_range", [default_threshold])
+    tie_threshold = self.config["metrics"]["model_selection"].get("tie_threshold", 0.0)
+    best = evaluate_maps(maps, all_labels, all_spacings, thresholds, tie_threshold,
+                         self._is_better_metric,
+                         body_masks=masks if any(m is not None for m in masks) else None,
+                         target_cache=state["targets"], case_keys=keys)
+    return 0.0, best
+
+
+def bind_validate(trainer_cls):
+    """Replace Trainer.validate (the original stays reachable as _l3u_reference_validate)."""
+    if _FALLBACK_VALIDATE not in trainer_cls.__dict__:
+        setattr(trainer_cls, _FALLBACK_VALIDATE, trainer_cls.validate)
+    trainer_cls.validate = validate
     return trainer_cls

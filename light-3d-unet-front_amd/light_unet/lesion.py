@@ -187,14 +187,16 @@ def _sizes0(c):
 
 
 def match_components(pred_labeled, target_labeled, iou_threshold=0.1, distance_threshold_mm=10.0,
-                     spacing=(4.0, 4.0, 4.0)):
+                     spacing=(4.0, 4.0, 4.0), inter=None):
     """metrics.py:127-213: greedy matching of predicted to target components by IoU or centre
-    distance.  Labelled arrays (numpy / device, [D, H, W] or [B, D, H, W]) or Components."""
+    distance.  Labelled arrays (numpy / device, [D, H, W] or [B, D, H, W]) or Components.
+    inter: the (num_pred + 1, num_target + 1) overlap table when the caller has it already (the
+    threshold sweep counts every level's overlaps in one launch)."""
     pc, tc = _as_components(pred_labeled), _as_components(target_labeled)
     num_pred, num_target = pc.num, tc.num
     if num_pred == 0 or num_target == 0:
         return [], list(range(1, num_pred + 1)), list(range(1, num_target + 1))
-    intersection = _intersections(pc, tc)
+    intersection = _intersections(pc, tc) if inter is None else inter
     pred_sizes, target_sizes = _sizes0(pc), _sizes0(tc)
     union = pred_sizes[:, None] + target_sizes[None, :] - intersection
     iou_matrix = np.divide(intersection, union, out=np.zeros_like(intersection, dtype=np.float32),
@@ -227,12 +229,12 @@ def _squeeze(a):
     return a
 
 
-def _lesion_counts(pc, tc, iou_threshold, distance_threshold_mm, spacing):
+def _lesion_counts(pc, tc, iou_threshold, distance_threshold_mm, spacing, inter=None):
     if tc.num == 0:
         return (0, pc.num, 0)
     if pc.num == 0:
         return (0, 0, tc.num)
-    m, up, ut = match_components(pc, tc, iou_threshold, distance_threshold_mm, spacing)
+    m, up, ut = match_components(pc, tc, iou_threshold, distance_threshold_mm, spacing, inter)
     return (len(m), len(up), len(ut))
 
 
@@ -294,6 +296,236 @@ def calculate_metrics(predictions, labels, threshold=0.5, spacing=(4.0, 4.0, 4.0
             "voxel_wise_dsc_micro": dsc_micro, "voxel_wise_dsc_macro": dsc_macro,
             "fp_per_case": tot_fp / n if n > 0 else 0.0, "tp": tot_tp, "fp": tot_fp, "fn": tot_fn,
             "dsc": dsc_micro, "recall": recall, "precision": precision}
+
+
+# ------------------------------------------------------------------ the threshold sweep
+MAX_LEVELS = 32   # csrc/lesion.hip kMaxLv
+
+
+def level_map(prob, thresholds, mask=None, target=None, want_masked=False):
+    """l3u_thr_levels: `prob` (device float32, any shape; * `mask` in float32 when given) against
+    the strictly ascending float32 `thresholds` (1..32 of them).  Returns (level uint8 of prob's
+    shape, hist int64 device [(K + 1), 2]: voxels per (level, target >= 0.5), masked map or None)."""
+    thr = np.ascontiguousarray(thresholds, dtype=np.float32)
+    K = int(thr.size)
+    if not (1 <= K <= MAX_LEVELS) or not np.all(thr[1:] > thr[:-1]) or not np.all(np.isfinite(thr)):
+        raise ValueError(f"thresholds must be 1..{MAX_LEVELS} finite, strictly ascending float32 values")
+    nat.require_device(prob, mask, target)
+    for t in (prob, mask, target):
+        if t is not None and (t.dtype != torch.float32 or not t.is_contiguous()
+                              or t.numel() != prob.numel()):
+            raise ValueError("level_map takes contiguous float32 device tensors of one size")
+    dev = prob.device
+    level = torch.empty(prob.shape, dtype=torch.uint8, device=dev)
+    hist = torch.empty((K + 1, 2), dtype=torch.int64, device=dev)
+    masked = torch.empty_like(prob) if want_masked else None
+    thr_d = torch.from_numpy(thr).to(dev)
+    nat.call("l3u_thr_levels", prob.data_ptr(), nat.ptr(mask), nat.ptr(target), thr_d.data_ptr(), K,
+             level.data_ptr(), hist.data_ptr(), nat.ptr(masked), prob.numel(), nat.stream())
+    return level, hist, masked
+
+
+def label_levels(level, K, k0=0, prob=None, target=None):
+    """The K binarisations level >= k0 + k + 1 (k = 0..K-1) of one [D, H, W] level volume
+    (level_map), labelled side by side: one l3u_ccl_label_lv, one read-back of the K counts, one
+    l3u_ccl_stats_lv and -- with `target` (a Components of the same shape) -- one
+    l3u_ccl_pairs_lv, whatever K.  Returns ([Components per level], [overlap table per level] or
+    None); every Components is what label(p, thr[k0 + k]) returns (labels are views of one
+    [K, D, H, W] tensor; prob lands in stats[:, 10])."""
+    D, H, W = (int(v) for v in level.shape)
+    n = D * H * W
+    K, k0 = int(K), int(k0)
+    if not (K >= 1 and k0 >= 0 and k0 + K <= MAX_LEVELS):
+        raise ValueError(f"levels {k0}..{k0 + K} outside 0..{MAX_LEVELS}")
+    if level.dtype != torch.uint8 or not level.is_cuda or not level.is_contiguous():
+        raise ValueError("level must be a contiguous uint8 device tensor")
+    dev, st = level.device, nat.stream()
+    nch = nat.query("l3u_ccl_nchunks", n)
+    parent = torch.empty(K * n, dtype=torch.int32, device=dev)
+    lab = torch.empty((K, D, H, W), dtype=torch.int32, device=dev)
+    cnt = torch.empty(K * (nch + 1), dtype=torch.int32, device=dev)
+    offs_d = torch.empty(K + 1, dtype=torch.int32, device=dev)
+    nat.call("l3u_ccl_label_lv", level.data_ptr(), k0, K, parent.data_ptr(), lab.data_ptr(),
+             cnt.data_ptr(), offs_d.data_ptr(), D, H, W, st)
+    offs = offs_d.cpu().numpy().astype(np.int64)
+    total = int(offs[K])
+    stats = np.zeros((0, 12), dtype=np.uint64)
+    if total > 0:
+        if prob is not None and (prob.dtype != torch.float32 or prob.numel() != n
+                                 or not prob.is_contiguous()):
+            raise ValueError("prob must be a contiguous float32 tensor of the level volume's size")
+        sd = torch.empty(total * 12, dtype=torch.int64, device=dev)
+        nat.call("l3u_ccl_stats_lv", lab.data_ptr(), nat.ptr(prob), offs_d.data_ptr(), sd.data_ptr(),
+                 total, K, D, H, W, st)
+        stats = sd.view(total, 12).cpu().numpy().view(np.uint64)
+    comps = [Components(lab[k], int(offs[k + 1] - offs[k]), stats[int(offs[k]):int(offs[k + 1])])
+             for k in range(K)]
+    if target is None:
+        return comps, None
+    if tuple(target.labels.shape) != (D, H, W):
+        raise ValueError("target labelling and level volume differ in shape")
+    nt = target.num
+    if total == 0 or nt == 0:
+        return comps, [np.zeros((c.num + 1, nt + 1), dtype=np.int64) for c in comps]
+    inter = torch.zeros(int((total + K) * (nt + 1)), dtype=torch.int32, device=dev)
+    nat.call("l3u_ccl_pairs_lv", lab.data_ptr(), target.labels.data_ptr(), nt, offs_d.data_ptr(),
+             inter.data_ptr(), K, n, st)
+    flat = inter.cpu().numpy().astype(np.int64)
+    tables = []
+    for k in range(K):
+        lo = int(offs[k] + k) * (nt + 1)
+        tables.append(flat[lo:lo + (comps[k].num + 1) * (nt + 1)].reshape(comps[k].num + 1, nt + 1))
+    return comps, tables
+
+
+def _np_kind(a):
+    """'f32' / 'f64' for the dtypes numpy keeps as such in `prob_map * body_mask` with a float32
+    or float64 partner; None for anything whose numpy promotion is not reproduced here."""
+    dt = a.dtype
+    if isinstance(a, torch.Tensor):
+        dt = {torch.float32: np.float32, torch.float64: np.float64, torch.bool: np.bool_,
+              torch.uint8: np.uint8, torch.int8: np.int8, torch.int16: np.int16}.get(dt)
+        if dt is None:
+            return None
+    dt = np.dtype(dt)
+    if dt == np.float64:
+        return "f64"
+    if dt in (np.dtype(np.float32), np.dtype(np.bool_), np.dtype(np.uint8), np.dtype(np.int8),
+              np.dtype(np.int16)):
+        return "f32"
+    return None
+
+
+def _arr(a):
+    return a if isinstance(a, torch.Tensor) else np.asarray(a)
+
+
+def _host(a):
+    return a.detach().cpu().numpy() if isinstance(a, torch.Tensor) else np.asarray(a)
+
+
+def _aggregate(rows, n):
+    """calculate_metrics' accumulation (metrics.py:343-404) over per-case integer rows
+    (pred voxels, target voxels, overlap voxels, tp, fp, fn), in case order."""
+    smooth = 1e-6
+    tot_tp = tot_fp = tot_fn = 0
+    inter_sum = union_sum = 0.0
+    per_case = []
+    for ps, ts, inter, tp, fp, fn in rows:
+        inter_sum += inter
+        union_sum += ps + ts
+        per_case.append((2.0 * inter + smooth) / ((ps + ts) + smooth))
+        tot_tp += tp
+        tot_fp += fp
+        tot_fn += fn
+    dsc_micro = (2.0 * inter_sum + smooth) / (union_sum + smooth)
+    dsc_macro = np.mean(per_case) if per_case else 0.0
+    recall = tot_tp / (tot_tp + tot_fn) if (tot_tp + tot_fn) > 0 else 0.0
+    precision = tot_tp / (tot_tp + tot_fp) if (tot_tp + tot_fp) > 0 else 0.0
+    f1 = (2 * precision * recall) / (precision + recall) if (precision + recall) > 0 else 0.0
+    return {"lesion_wise_recall": recall, "lesion_wise_precision": precision, "lesion_wise_f1": f1,
+            "voxel_wise_dsc_micro": dsc_micro, "voxel_wise_dsc_macro": dsc_macro,
+            "fp_per_case": tot_fp / n if n > 0 else 0.0, "tp": tot_tp, "fp": tot_fp, "fn": tot_fn,
+            "dsc": dsc_micro, "recall": recall, "precision": precision}
+
+
+def _sweep_case(pred, mask, tc, thr32, thr64, spacing, dev, max_workspace_bytes):
+    """One case of sweep_metrics: rows[k] = (pred voxels, target voxels, overlap voxels, tp, fp,
+    fn) at the k-th of the sorted distinct thresholds."""
+    K = len(thr32)
+    pv = _volume(pred, dev, keep_f64=True)
+    mv = None
+    if mask is not None:
+        mv = _volume(mask, dev, keep_f64=True)
+        if tuple(mv.shape) != tuple(pv.shape):
+            raise ValueError("body mask and prediction differ in shape")
+    tfg = (tc.labels > 0).to(torch.float32)   # target >= 0.5, as label(target, 0.5) classified it
+    if pv.dtype == torch.float64 or (mv is not None and mv.dtype == torch.float64):
+        # the reference compares a float64 map (or float64 product) in float64 (_foreground):
+        # the levels are counted in float64 here and go through the same level kernels as the
+        # "map" level with thresholds 1..K
+        q = pv.double() if mv is None else pv.double() * mv.double()
+        lv = torch.zeros(q.shape, dtype=torch.float32, device=dev)
+        for t in thr64:
+            lv += (q >= t).to(torch.float32)
+        pv, mv, thr_k = lv, None, np.arange(1, K + 1, dtype=np.float32)
+    else:
+        thr_k = thr32
+    level, hist, _ = level_map(pv, thr_k, mask=mv, target=tfg)
+    n = pv.numel()
+    G = max(1, min(K, nat.query("l3u_ccl_lv_max_levels", n, int(max_workspace_bytes))))
+    counts = []
+    for k0 in range(0, K, G):
+        comps, tables = label_levels(level, min(G, K - k0), k0=k0, target=tc)
+        for pc, inter in zip(comps, tables):
+            counts.append(_lesion_counts(pc, tc, 0.1, 10.0, spacing, inter))
+    h = hist.cpu().numpy()
+    ge = np.cumsum(h[::-1], axis=0)[::-1]   # ge[l] = voxels with level >= l, per target class
+    ts = int(h[:, 1].sum())
+    return [(int(ge[k + 1].sum()), ts, int(ge[k + 1, 1])) + counts[k] for k in range(K)]
+
+
+def sweep_metrics(predictions, labels, thresholds, spacing=(4.0, 4.0, 4.0), body_masks=None,
+                  target_cache=None, case_keys=None, max_workspace_bytes=1 << 30):
+    """[calculate_metrics(predictions (* body_masks), labels, threshold=t, spacing) for t in
+    thresholds], key for key and bit for bit, from ONE pass per case: one l3u_thr_levels (the
+    level encoding of all distinct float32 thresholds and the voxel histogram DSC needs), one
+    level-batched labelling / statistics / overlap launch each (label_levels) and one labelling of
+    the target -- none when `target_cache` (a dict) holds it already under the case's key
+    (`case_keys`, default the position; entries are checked against the label's shape).  The
+    number of native calls per case does not depend on the number of thresholds; when the K level
+    workspaces exceed `max_workspace_bytes` the levels run in groups.  Cases are numpy arrays or
+    device tensors.  Inputs the level kernels do not take (a [B, D, H, W] case with B > 1, more
+    than 32 distinct thresholds, dtypes numpy would promote differently) loop calculate_metrics."""
+    thresholds = [t for t in thresholds]
+    pred_list, label_list = _case_list(predictions, "predictions"), _case_list(labels, "labels")
+    n_cases = len(pred_list)
+    mask_list = [None] * n_cases if body_masks is None else _case_list(body_masks, "body_masks")
+    if len(mask_list) != n_cases:
+        raise ValueError("body_masks must hold one entry (or None) per case")
+    if not thresholds:
+        return []
+    preds = [_squeeze(_arr(p)) for p in pred_list]
+    targets = [_squeeze(_arr(t)) for t in label_list]
+    masks = [None if m is None else _squeeze(_arr(m)) for m in mask_list]
+    tf = np.asarray([float(t) for t in thresholds], dtype=np.float64)
+    thr32 = np.unique(tf.astype(np.float32))
+    fast = bool(np.all(np.isfinite(tf))) and len(thr32) <= MAX_LEVELS and len(label_list) == n_cases
+    any64 = False
+    for p, t, m in zip(preds, targets, masks):
+        kinds = [_np_kind(p)] + ([] if m is None else [_np_kind(m)])
+        floating = p.dtype in (torch.float32, torch.float64) if isinstance(p, torch.Tensor) \
+            else p.dtype in (np.dtype(np.float32), np.dtype(np.float64))
+        fast = fast and floating and None not in kinds and len(p.shape) == 3 \
+            and tuple(t.shape) == tuple(p.shape) and (m is None or tuple(m.shape) == tuple(p.shape))
+        any64 = any64 or "f64" in kinds
+    # float64 comparisons use the thresholds as given: one float64 value per distinct float32 one
+    thr64 = sorted(set(tf.tolist()))
+    if any64 and len(thr64) != len(thr32):
+        fast = False
+    if not fast:
+        host = [_host(p) if m is None else _host(p) * _host(m) for p, m in zip(pred_list, mask_list)]
+        return [calculate_metrics(host, [_host(t) for t in label_list], threshold=t, spacing=spacing)
+                for t in thresholds]
+    spacings = _spacing_per_case(spacing, n_cases)
+    dev = _device()
+    keys = list(range(n_cases)) if case_keys is None else list(case_keys)
+    per_case = []
+    for i, (p, t, m, sp) in enumerate(zip(preds, targets, masks, spacings)):
+        shape = tuple(int(v) for v in t.shape)
+        hit = target_cache.get(keys[i]) if target_cache is not None else None
+        if hit is not None and hit[0] == shape:
+            tc = hit[1]
+        else:
+            tc = label(t, 0.5)
+            if target_cache is not None:
+                target_cache[keys[i]] = (shape, tc)
+        per_case.append(_sweep_case(p, m, tc, thr32, thr64, sp, dev, max_workspace_bytes))
+    out = []
+    for t in thresholds:
+        k = int(np.searchsorted(thr32, np.float32(t)))
+        out.append(_aggregate([rows[k] for rows in per_case], n_cases))
+    return out
 
 
 def _case_list(x, what):

@@ -80,11 +80,67 @@ class _GraphForward:
         return self.model(self.x)
 
 
+class _CachedForward:
+    """The network forward of a fixed window batch as a graph that outlives one volume
+    (`forward_cache`): only the network is captured, on one static input buffer and the model's
+    flat parameter buffer; the gather -- which has the volume's pointer and dimensions in its
+    arguments -- runs eagerly before each replay.  Same kernels on the same values as
+    _GraphForward, so the result is bitwise the same."""
+    captures = 0   # graphs captured so far (tests count these)
+
+    def __init__(self, model, patch, batch, device):
+        self.model, self.patch, self.batch = model, patch, batch
+        self.pos = torch.zeros(batch, 3, dtype=torch.int32, device=device)
+        self.x = torch.empty(batch, 1, *patch, device=device)
+        self.engine = model.engine
+        self.flat = model.flat_parameters()
+        self.x.zero_()
+        side = torch.cuda.Stream(device=device)
+        side.wait_stream(torch.cuda.current_stream(device))
+        with torch.cuda.stream(side):
+            self.engine.forward(self.flat, self.x, training=False, save=False)
+        torch.cuda.current_stream(device).wait_stream(side)
+        self.graph = torch.cuda.CUDAGraph()
+        with torch.cuda.graph(self.graph):
+            self.out, _ = self.engine.forward(self.flat, self.x, training=False, save=False)
+        _CachedForward.captures += 1
+        self.vol = self.dims = None
+
+    def bind(self, vol, D, H, W):
+        self.vol, self.dims = vol, (D, H, W)
+        return self
+
+    def __call__(self):
+        D, H, W = self.dims
+        nat.call("l3u_window_gather", self.vol.data_ptr(), D, H, W, self.pos.data_ptr(), self.batch,
+                 *self.patch, self.x.data_ptr(), nat.stream())
+        self.graph.replay()
+        return self.out
+
+
+def _forward_for(model, vol, d, h, w, patch, B, device, forward_cache):
+    """The window-batch forward: a fresh _GraphForward, or with `forward_cache` (a dict) the
+    cached network graph of (model identity, window batch, patch, activation dtype)."""
+    engine = getattr(model, "engine", None)
+    if forward_cache is None or engine is None:
+        return _GraphForward(model, vol, d, h, w, patch, B, device)
+    # the engine's current activation storage, which is what _GraphForward would capture with
+    key = (id(model), int(B), tuple(patch), str(engine.act_dtype))
+    fwd = forward_cache.get(key)
+    # the graph reads the flat parameter buffer it was captured on: a re-flattened model
+    # (new storage) gets a new capture
+    if fwd is None or fwd.model is not model or \
+            fwd.flat.data_ptr() != model.flat_parameters().data_ptr():
+        fwd = _CachedForward(model, patch, B, device)
+        forward_cache[key] = fwd
+    return fwd.bind(vol, d, h, w)
+
+
 def sliding_window_inference_3d(image: np.ndarray, model: torch.nn.Module,
                                 patch_size: Tuple[int, int, int] = (48, 48, 48),
                                 overlap: float = 0.5, device: torch.device = None,
                                 use_gaussian: bool = True, window_batch: int = 16,
-                                group=None) -> np.ndarray:
+                                group=None, output: str = "numpy", forward_cache=None):
     """utils.py:11-139.  `window_batch` windows run per forward (extra keyword; the result
     does not depend on it).
 
@@ -93,7 +149,16 @@ def sliding_window_inference_3d(image: np.ndarray, model: torch.nn.Module,
     round-robin.  Each rank blends only its own windows' predictions (the others count as
     zero; the denominator sum(importance) is the full one everywhere), and one all_reduce(SUM)
     of the [D, H, W] map (RCCL over xGMI) adds the shares: the result equals the one-GPU map
-    up to the order of the fp32 additions."""
+    up to the order of the fp32 additions.
+
+    `image` may also be a float32 tensor already on `device` (it is then not uploaded).
+    `output="device"` returns the [D, H, W] float32 device tensor instead of copying it to the
+    host.  `forward_cache` (a dict the caller keeps, e.g. across the cases and epochs of a
+    validation) stores the captured network forward, so later calls with the same model, window
+    batch, patch and activation dtype replay it instead of capturing again; the result is bitwise
+    the uncached one."""
+    if output not in ("numpy", "device"):
+        raise ValueError(f"output must be 'numpy' or 'device', got {output!r}")
     if device is None:
         device = next(model.parameters()).device
     device = torch.device(device)
@@ -118,7 +183,10 @@ def sliding_window_inference_3d(image: np.ndarray, model: torch.nn.Module,
     model.eval()
     try:
         with torch.no_grad():
-            vol = torch.from_numpy(np.ascontiguousarray(image, dtype=np.float32)).to(device)
+            if isinstance(image, torch.Tensor):
+                vol = image.to(device=device, dtype=torch.float32).contiguous()
+            else:
+                vol = torch.from_numpy(np.ascontiguousarray(image, dtype=np.float32)).to(device)
             pos_all = torch.tensor(order + [order[-1]] * ((-nwin) % B), dtype=torch.int32,
                                    device=device)
             world, rank = 1, 0
@@ -126,7 +194,7 @@ def sliding_window_inference_3d(image: np.ndarray, model: torch.nn.Module,
                 import torch.distributed as dist
                 world, rank = dist.get_world_size(group), dist.get_rank(group)
             preds = (torch.zeros if world > 1 else torch.empty)(pos_all.shape[0], P, device=device)
-            fwd = _GraphForward(model, vol, d, h, w, (pd, ph, pw), B, device)
+            fwd = _forward_for(model, vol, d, h, w, (pd, ph, pw), B, device, forward_cache)
             for bi, b0 in enumerate(range(0, nwin, B)):
                 if bi % world != rank:   # another rank's batch
                     continue
@@ -143,6 +211,6 @@ def sliding_window_inference_3d(image: np.ndarray, model: torch.nn.Module,
                      prob.data_ptr(), nat.stream())
             if world > 1:
                 dist.all_reduce(prob, op=dist.ReduceOp.SUM, group=group)
-            return prob.cpu().numpy()
+            return prob if output == "device" else prob.cpu().numpy()
     finally:
         model.train(was_training)
