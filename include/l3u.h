@@ -817,6 +817,47 @@ int l3u_convt_bwd_bf16(const float* dy, long long dy_nstride, const l3u_bf16* x,
                        float* wpart, float* bpart, int N, int Ci, int Co, int D, int H, int W,
                        hipStream_t stream);
 
+/* ---- case preprocessing (csrc/preprocess.hip; the reference's scripts/preprocess_data.py) ----
+ * l3u_pp_select: the order statistics of src[n] (float, or double when is_f64) at the 0-based
+ * ranks r0..r(nranks-1) (1..4 of them, each < n), bit-exact, as doubles into out[0..nranks-1]
+ * (a float widens exactly); out[4] receives the number of NaNs in src (they are left out of the
+ * ranking: the caller decides what that means).  -0 ranks as +0.  A most-significant-digit-first
+ * radix descent over monotone integer keys: per 8-bit digit one histogram sweep (LDS histogram per
+ * workgroup, integer atomics: exact and order-independent) and one single-workgroup launch that
+ * picks each rank's bin; 4 sweeps for float, 8 for double, no host round trip and no compaction.
+ * ws: l3u_pp_select_ws_bytes() bytes of device workspace (cleared by the call).  out: 5 doubles.
+ *
+ * l3u_pp_normalize: v = (clip(x, lo, hi) - lo) / (hi - lo) * scale + t0 per voxel in fp64, each
+ * operation rounded on its own (no fused multiply-add), with lo = clip[0], hi = clip[1] read from
+ * device memory (hi > lo).  Writes v to out64 and / or its float rounding to out32 and / or the
+ * packed mask v > threshold (compared in fp64) to bits; any of the three may be NULL.
+ *
+ * Packed masks: one bit per voxel of a [D, H, W] volume, x fastest; a row (z, y) is
+ * ceil(W / 64) 64-bit words, bit i of word wx is x = 64 * wx + i, padding bits are 0.
+ * l3u_pp_pack: bits from src of dtype 0 float, 1 double, 2 uint8, 3 int32 with op 0: v != 0,
+ * 1: v > arg, 2: v == arg (compared as doubles).  l3u_pp_unpack: 0 / 1 into dst of dtype 0 float
+ * or 2 uint8.
+ * l3u_pp_morph: `iters` iterations (1..l3u_pp_morph_max_iters(W)) of dilation (erode = 0) or
+ * erosion (erode = 1) with the 6-neighbour cross, in one launch; everything outside the volume
+ * reads as 0 at every iteration, for erosion too.  in != out.
+ * l3u_pp_mask_stats: stats[7] int64 = set voxels, min z, y, x, max z, y, x (min 2^31 - 1 and
+ * max -1 for an empty mask). */
+int l3u_pp_select_ws_bytes(void);
+int l3u_pp_select(const void* src, int is_f64, long long n, int nranks, long long r0, long long r1,
+                  long long r2, long long r3, void* ws, double* out, hipStream_t stream);
+int l3u_pp_normalize(const void* src, int is_f64, const double* clip, double scale, double t0,
+                     double threshold, double* out64, float* out32, unsigned long long* bits, int D,
+                     int H, int W, hipStream_t stream);
+int l3u_pp_pack(const void* src, int dtype, int op, double arg, unsigned long long* bits, int D,
+                int H, int W, hipStream_t stream);
+int l3u_pp_unpack(const unsigned long long* bits, void* dst, int dtype, int D, int H, int W,
+                  hipStream_t stream);
+int l3u_pp_morph_max_iters(int W);
+int l3u_pp_morph(const unsigned long long* in, unsigned long long* out, int erode, int iters, int D,
+                 int H, int W, hipStream_t stream);
+int l3u_pp_mask_stats(const unsigned long long* bits, long long* stats, int D, int H, int W,
+                      hipStream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -156,29 +156,69 @@ __global__ __launch_bounds__(256) void ccl_stats_kernel(int* __restrict__ label,
                                                         unsigned long long* __restrict__ stats,
                                                         int B, int D, int H, int W, int lead4) {
   const long long S = (long long)D * H * W, n = B * S, HW = (long long)H * W;
-  for (long long i = blockIdx.x * 256ll + threadIdx.x; i < n; i += (long long)gridDim.x * 256) {
-    int l = label[i];
-    if (l <= 0) continue;
-    if (remap) {
+  const int lane = threadIdx.x & 63;
+  // whole waves run the loop together: a wave whose labelled lanes all carry ONE label (the inside
+  // of a large component; a body mask is one component of millions of voxels) reduces its lanes
+  // first and issues one set of atomics, instead of 64 colliding ones per statistic.  Integer
+  // sums / minima / maxima: the same results in any grouping.
+  const long long nround = (n + 63) & ~63ll;
+  for (long long i = blockIdx.x * 256ll + threadIdx.x; i < nround; i += (long long)gridDim.x * 256) {
+    int l = i < n ? label[i] : 0;
+    if (l > 0 && remap) {
       l = remap[l];
       label[i] = l;
-      if (l <= 0) continue;
     }
-    const long long r = i % S;
-    const unsigned long long x = r % W, y = (r / W) % H, z = r / HW, b = i / S;
+    const bool on = l > 0;
+    const unsigned long long bm = __ballot(on);
+    if (bm == 0) continue;
+    const long long ic = i < n ? i : 0;
+    const long long r = ic % S;
+    const unsigned long long x = r % W, y = (r / W) % H, z = r / HW, b = ic / S;
     const unsigned long long c0 = lead4 ? b : z, c1 = lead4 ? z : y, c2 = lead4 ? y : x;
-    unsigned long long* s = stats + (long long)(l - 1) * 12;
-    atomicAdd(s + 0, 1ull);
-    atomicAdd(s + 1, c0);
-    atomicAdd(s + 2, c1);
-    atomicAdd(s + 3, c2);
-    atomicMin(s + 4, c0);
-    atomicMin(s + 5, c1);
-    atomicMin(s + 6, c2);
-    atomicMax(s + 7, c0);
-    atomicMax(s + 8, c1);
-    atomicMax(s + 9, c2);
-    if (prob) atomicMax(s + 10, (unsigned long long)__float_as_uint(fmaxf(prob[i], 0.f)));
+    unsigned long long pm = 0;
+    if (on && prob) pm = (unsigned long long)__float_as_uint(fmaxf(prob[i], 0.f));
+    const int first = __builtin_ctzll(bm);
+    const int l0 = __builtin_amdgcn_readlane(l, first);
+    if (__ballot(on && l == l0) == bm && __builtin_popcountll(bm) > 1) {
+      unsigned long long v[10] = {on ? c0 : 0ull, on ? c1 : 0ull, on ? c2 : 0ull,
+                                  on ? c0 : ~0ull, on ? c1 : ~0ull, on ? c2 : ~0ull,
+                                  on ? c0 : 0ull, on ? c1 : 0ull, on ? c2 : 0ull, pm};
+#pragma unroll
+      for (int m = 1; m < 64; m <<= 1) {
+#pragma unroll
+        for (int k = 0; k < 10; ++k) {
+          const unsigned long long o = __shfl_xor(v[k], m);
+          v[k] = k < 3 ? v[k] + o : (k < 6 ? (o < v[k] ? o : v[k]) : (o > v[k] ? o : v[k]));
+        }
+      }
+      if (lane == first) {
+        unsigned long long* s = stats + (long long)(l0 - 1) * 12;
+        atomicAdd(s + 0, (unsigned long long)__builtin_popcountll(bm));
+        atomicAdd(s + 1, v[0]);
+        atomicAdd(s + 2, v[1]);
+        atomicAdd(s + 3, v[2]);
+        atomicMin(s + 4, v[3]);
+        atomicMin(s + 5, v[4]);
+        atomicMin(s + 6, v[5]);
+        atomicMax(s + 7, v[6]);
+        atomicMax(s + 8, v[7]);
+        atomicMax(s + 9, v[8]);
+        if (prob) atomicMax(s + 10, v[9]);
+      }
+    } else if (on) {
+      unsigned long long* s = stats + (long long)(l - 1) * 12;
+      atomicAdd(s + 0, 1ull);
+      atomicAdd(s + 1, c0);
+      atomicAdd(s + 2, c1);
+      atomicAdd(s + 3, c2);
+      atomicMin(s + 4, c0);
+      atomicMin(s + 5, c1);
+      atomicMin(s + 6, c2);
+      atomicMax(s + 7, c0);
+      atomicMax(s + 8, c1);
+      atomicMax(s + 9, c2);
+      if (prob) atomicMax(s + 10, pm);
+    }
   }
 }
 

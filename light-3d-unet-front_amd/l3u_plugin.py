@@ -51,6 +51,7 @@ def load():
     importlib.import_module(ALIAS + ".fast_trainer")
     importlib.import_module(ALIAS + ".lesion")
     importlib.import_module(ALIAS + ".patches")
+    importlib.import_module(ALIAS + ".preprocess")
     return mod
 
 
@@ -93,6 +94,26 @@ def _bind_lesion(done):
                                       self.config["data"]["bbox_expansion_voxels"])
         inf.Inferencer.extract_bboxes = extract_bboxes
         done.setdefault("light_unet.core.inferencer", []).append("Inferencer.extract_bboxes")
+
+
+PREPROCESS = ("clip_and_normalize", "generate_body_mask", "calculate_voxel_thresholds")
+
+
+def bind_preprocess(module):
+    """The device preprocessing (light_unet/preprocess.py) into a module object the caller
+    imported -- the reference's scripts/preprocess_data.py is a script, not part of its package:
+
+        spec = importlib.util.spec_from_file_location("preprocess_data", ".../scripts/preprocess_data.py")
+        pp = importlib.util.module_from_spec(spec); spec.loader.exec_module(pp)
+        l3u_plugin.bind_preprocess(pp)          # preprocess_case / preprocess_dataset now call these
+
+    Sets clip_and_normalize, generate_body_mask and calculate_voxel_thresholds (same signatures
+    and results, preprocess_data.py:21-174) and returns the names it bound."""
+    load()
+    pre = sys.modules[ALIAS + ".preprocess"]
+    for n in PREPROCESS:
+        setattr(module, n, getattr(pre, n))
+    return list(PREPROCESS)
 
 
 def _bind_device_patches(done):

@@ -121,6 +121,15 @@ _SIGS = {
     "l3u_outconv_bwd_loss4_dz": [P, P, P] + _FAM + [P, P, L, P, P, L, P, P, I, I, I, P],
     "l3u_outconv_bwd_loss4p": [P, P, P, I] + _FAM + [P, P, L, P, P, L, P, P, I, I, I, P],
     "l3u_outconv_bwd_loss4p_dz": [P, P, P, I] + _FAM + [P, P, L, P, P, L, P, P, I, I, I, P],
+    # case preprocessing: order statistics, fp64 normalise, packed masks and their morphology
+    "l3u_pp_select_ws_bytes": [],
+    "l3u_pp_select": [P, I, L, I, L, L, L, L, P, P, P],
+    "l3u_pp_normalize": [P, I, P, D, D, D, P, P, P, I, I, I, P],
+    "l3u_pp_pack": [P, I, I, D, P, I, I, I, P],
+    "l3u_pp_unpack": [P, P, I, I, I, I, P],
+    "l3u_pp_morph_max_iters": [I],
+    "l3u_pp_morph": [P, P, I, I, I, I, I, P],
+    "l3u_pp_mask_stats": [P, P, I, I, I, P],
 }
 # entry points with a _bf16 twin (same arguments; saved activations stored as bf16, gradients
 # fp32, include/l3u.h)
@@ -144,7 +153,7 @@ _QUERIES = {"l3u_abi_version", "l3u_dw3_nchunk", "l3u_pw_stat_nsb", "l3u_pw_bwd_
             "l3u_gconv3_nblocks", "l3u_gconv3_wgrad_nparts", "l3u_front_nblocks",
             "l3u_ccl_nchunks", "l3u_dwpw_supported", "l3u_dwpw_stat_nsb",
             "l3u_dw3_bwd_rank1", "l3u_pw_bwd2_supported", "l3u_pw_bwd_chunk",
-            "l3u_ccl_lv_max_levels"}
+            "l3u_ccl_lv_max_levels", "l3u_pp_select_ws_bytes", "l3u_pp_morph_max_iters"}
 
 _lib = None
 
