@@ -395,6 +395,104 @@ int l3u_aug_patches(const l3u_aug_param* params, int B, int pz, int py, int px, 
                     float* tmp_img, float* tmp_lab, float* out_img, float* out_lab,
                     hipStream_t stream);
 
+/* ---- Training-patch draws on the device (csrc/augdraw.hip) -----------------------------------
+ * The random decisions behind a batch of training patches -- PatchDataset.__getitem__'s location
+ * draw (patch_dataset.py:115-124), MixedPatchDataset's domain draw (:254-261) and _augment's
+ * draws (:156-220) -- made by a stateless counter-based generator, so a captured launch chain
+ * (l3u_aug_draw -> l3u_aug_patches -> l3u_counter_add(step, 1)) draws a fresh batch per replay.
+ * Same distribution as the host draws of light_unet/patches.py, a different sample.
+ *
+ * The generator.  S = splitmix64 (the 64-bit finalizer of csrc/common.h: z += 0x9E3779B97F4A7C15;
+ * z = (z ^ z >> 30) * 0xBF58476D1CE4E5B9; z = (z ^ z >> 27) * 0x94D049BB133111EB; z ^ z >> 31),
+ * all arithmetic mod 2^64:
+ *   key(seed, step, item) = S(seed ^ S((uint32(step) << 32) | uint32(item)))
+ *   h(slot, v)            = S(key ^ S((v << 8) | slot))     slot < 256: L3U_DRAW_*; v = 0 except
+ *                                                           for the noise slots (v = voxel index
+ *                                                           in the patch, z-major)
+ *   unit u                = (h >> 11) * 2^-53               in [0, 1)
+ *   choice among n        = (h * n) >> 64                   high 64 bits of the 128-bit product
+ *   range [lo, hi)        = lo + (hi - lo) * u              fp64; difference, product and sum each
+ *                                                           rounded on its own (numpy's uniform)
+ *   noise[v]              = sigma * (sqrt(-2 * ln u1) * cos(6.283185307179586 * u2)),  fp64,
+ *                           u1 = ((h(NOISE_U1, v) >> 11) + 1) * 2^-53 in (0, 1],
+ *                           u2 = unit of h(NOISE_U2, v)     (Box-Muller, mean 0)
+ * Decisions per item, every probability test `u < prob` (slots in the order they are used):
+ *   two domains (FL = 0, DLBCL = 1; len = n_lesion + n_background of a domain's tables):
+ *     u(DOMAIN) < fl_ratio and len(FL) > 0 -> FL, counts[0] += 1; else len(DLBCL) > 0 -> DLBCL,
+ *     counts[1] += 1; else FL (not counted).  One domain: domain 0, no draw, counts untouched.
+ *   u(TABLE) < lesion_ratio and n_lesion > 0 -> lesion table; else n_background > 0 -> background
+ *     table; else lesion table.  Row = choice(LOCATION) among the table's rows (case, z, y, x).
+ *   flip: on and u(FLIP_ON) < prob -> axis = axes[choice(FLIP_AXIS)]
+ *   rotation: on and u(ROT_ON) < prob -> angle = range(ROT_ANGLE), plane = planes[choice(ROT_PLANE)]
+ *   scale / shift: on and u(*_ON) < prob -> range(SCALE / SHIFT);   noise: on and u(NOISE_ON) < prob.
+ * The l3u_aug_param record is then formed as light_unet/patches.py aug_param forms it: crop start
+ * max(0, c - p / 2) (integer division); the plane's axes sorted; rot_c / rot_s = cos / sin of
+ * angle * (pi / 180) (exact at multiples of 90 degrees) and the offsets ic - R ic with
+ * ic = (p - 1) / 2; zs = rint(p * scale) (half to even), zst = (zs - p) / 2 when zs > p else 0,
+ * zf = (p - 1) / (zs - 1), 1 when zs == 1; shift rounded to float.  Unused fields are 0 (axes -1). */
+#define L3U_DRAW_DOMAIN 0
+#define L3U_DRAW_TABLE 1
+#define L3U_DRAW_LOCATION 2
+#define L3U_DRAW_FLIP_ON 3
+#define L3U_DRAW_FLIP_AXIS 4
+#define L3U_DRAW_ROT_ON 5
+#define L3U_DRAW_ROT_ANGLE 6
+#define L3U_DRAW_ROT_PLANE 7
+#define L3U_DRAW_SCALE_ON 8
+#define L3U_DRAW_SCALE 9
+#define L3U_DRAW_SHIFT_ON 10
+#define L3U_DRAW_SHIFT 11
+#define L3U_DRAW_NOISE_ON 12
+#define L3U_DRAW_NOISE_U1 13
+#define L3U_DRAW_NOISE_U2 14
+#define L3U_DRAW_MAX_AXES 8   /* entries of a flip-axis / rotation-plane list */
+
+typedef struct l3u_aug_case {      /* one case volume resident on the device, [sd][sh][sw] fp32 */
+  const float* image;
+  const float* label;
+  int sd, sh, sw;
+  int pad;
+} l3u_aug_case;
+
+typedef struct l3u_aug_tables {    /* one dataset (domain); every pointer is device memory */
+  const l3u_aug_case* cases;
+  const int* lesion;               /* [n_lesion][4] = (case, z, y, x) */
+  const int* background;           /* [n_background][4] */
+  int n_lesion, n_background;
+} l3u_aug_tables;
+
+typedef struct l3u_aug_cfg {       /* PatchDataset's lesion_patch_ratio and augmentation config */
+  double lesion_ratio;
+  double flip_prob, rot_prob, scale_prob, shift_prob, noise_prob;
+  double rot_lo, rot_hi, scale_lo, scale_hi, shift_lo, shift_hi, noise_sigma;
+  int flip_on, rot_on, scale_on, shift_on, noise_on;
+  int flip_naxes, rot_nplanes;     /* 1..L3U_DRAW_MAX_AXES where the augmentation is on */
+  int flip_axes[L3U_DRAW_MAX_AXES];
+  int rot_planes[L3U_DRAW_MAX_AXES][2];
+  int pad;
+} l3u_aug_cfg;
+
+typedef struct l3u_aug_draw_rec {  /* what was drawn for one item, before any derived constant */
+  int domain, case_idx, table;     /* table 0 lesion, 1 background */
+  int loc;                         /* row of that table */
+  int cz, cy, cx;                  /* the row's centre */
+  int flip_on, flip_axis;          /* axis -1 when off */
+  int rot_on, rot_a0, rot_a1;      /* the plane as listed in the config (unsorted); -1 when off */
+  int scale_on, shift_on, noise_on;
+  int step;                        /* the value of *step the item was drawn at */
+  double angle, scale, shift;      /* 0 when off */
+} l3u_aug_draw_rec;
+
+/* tables[ndom], cfgs[ndom] (ndom 1 or 2; host structs, passed to the kernels by value: the call
+ * reads no device memory on the host and allocates nothing).  step: device counter, read by the
+ * kernels, NOT advanced here (l3u_counter_add).  recs[B], params[B], noise[B][pz][py][px] (written
+ * for the items whose noise is on only) and counts[2] (int32, accumulated with atomicAdd; may be
+ * NULL) are device memory.  Two launches: one thread per item, then one per voxel for the noise. */
+int l3u_aug_draw(const l3u_aug_tables* tables, const l3u_aug_cfg* cfgs, int ndom, double fl_ratio,
+                 unsigned long long seed, const int* step, int B, int pz, int py, int px,
+                 l3u_aug_draw_rec* recs, l3u_aug_param* params, double* noise, int* counts,
+                 hipStream_t stream);
+
 /* ---- Lesion post-processing (light_unet/models/metrics.py:38-63,107-213;
  *      light_unet/core/inferencer.py:62-111) -------------------------------------------------
  * l3u_ccl_label: connected components of (src >= threshold) over the 6 face neighbours

@@ -116,18 +116,22 @@ def bind_preprocess(module):
     return list(PREPROCESS)
 
 
-def _bind_device_patches(done):
+DEVICE_PATCHES = (False, True, "device_draws")
+
+
+def _bind_device_patches(done, draws="host"):
     """The training loaders of light_unet.datasets.loader (get_data_loader, loader.py:99-113)
     on device patches: loader._create_train_loader (loader.py:9-10, called by the standard,
     step-based and probabilistic factories) returns a DevicePatchLoader over the device twin of
     the PatchDataset / MixedPatchDataset the factory just built (its cases read once into HBM,
-    its sampled locations kept; l3u_amd.patches).  Validation loaders are unchanged."""
+    its sampled locations kept; l3u_amd.patches).  Validation loaders are unchanged.
+    draws="device": the loaders' per-item draws are made on the device as well."""
     loader = importlib.import_module("light_unet.datasets.loader")
     patches = sys.modules[ALIAS + ".patches"]
     ref = getattr(loader._create_train_loader, "_l3u_reference", loader._create_train_loader)
 
     def _create_train_loader(dataset, batch_size, shuffle=True):
-        return patches.device_loader(dataset, batch_size)
+        return patches.device_loader(dataset, batch_size, draws=draws)
     _create_train_loader._l3u_reference = ref
     loader._create_train_loader = _create_train_loader
     done["light_unet.datasets.loader"] = ["_create_train_loader"]
@@ -151,6 +155,11 @@ def install(fast_step=False, lesion=True, device_patches=False, fast_validate=Fa
     and augment their patches on the device (light_unet/patches.py; num_workers = 0 draw
     semantics, DevicePatchLoader), so the graph-replayed step never waits on host workers or a
     PCIe copy.  Needs light_unet.datasets.loader (and its NIfTI reader).
+    device_patches="device_draws" makes the same loaders draw on the device too (l3u_aug_draw:
+    a counter-based generator seeded with the dataset's seed and the data-parallel rank), each
+    full batch one hipGraph replay with no host RNG call, upload or sync: a third patch stream,
+    the same distribution as the host draws but different samples; the global numpy / python
+    RNGs are left alone.  Any other value raises ValueError.
 
     fast_validate=True also replaces Trainer.validate (trainer.py:349-445) with
     light_unet/fast_trainer.py's: probability maps stay on the device from the sliding window to
@@ -159,6 +168,8 @@ def install(fast_step=False, lesion=True, device_patches=False, fast_validate=Fa
     case (lesion.sweep_metrics).  Same return value; the original stays reachable as
     Trainer._l3u_reference_validate.  Needs light_unet.core.trainer."""
 
+    if isinstance(device_patches, str) and device_patches != "device_draws":
+        raise ValueError(f"device_patches must be one of {DEVICE_PATCHES}, got {device_patches!r}")
     amd = load()
     trainer_mod = (importlib.import_module("light_unet.core.trainer")
                    if (fast_step or fast_validate) else None)
@@ -190,7 +201,7 @@ def install(fast_step=False, lesion=True, device_patches=False, fast_validate=Fa
         fast.bind_validate(trainer_mod.Trainer)
         done.setdefault("light_unet.core.trainer", []).append("Trainer.validate")
     if device_patches:
-        _bind_device_patches(done)
+        _bind_device_patches(done, "device" if device_patches == "device_draws" else "host")
     if lesion:
         _bind_lesion(done)
     amd.installed_into = done

@@ -22,6 +22,9 @@ rank 0 writes checkpoints (the weights are identical on every rank after each st
 all-reduce).  Unlike scripts/train.py:55 the config file is never rewritten.
 `--fast-validate` runs that rank-0 validation on device-resident probability maps
 (l3u_plugin.install(fast_validate=True): cached forward graph, one threshold sweep per case).
+`--device-draws` makes the training loaders draw, cut and augment their patches on the device
+(l3u_plugin.install(device_patches="device_draws"): a counter-based stream seeded per rank, one
+graph replay per batch; the numpy / python seeds below then only drive whatever else uses them).
 """
 import argparse
 import os
@@ -65,6 +68,10 @@ def main(argv=None):
     ap.add_argument("--device-patches", action="store_true",
                     help="cut and augment training patches on the device (l3u_amd.patches; "
                          "num_workers = 0 draw semantics, per-rank RNG streams)")
+    ap.add_argument("--device-draws", action="store_true",
+                    help="device patches whose random draws are made on the device as well "
+                         "(l3u_aug_draw: counter-based, seeded per rank; every batch one graph "
+                         "replay, no host RNG); implies --device-patches")
     ap.add_argument("--fast-validate", action="store_true",
                     help="device-resident validation: cached forward graph and one threshold "
                          "sweep per case (l3u_amd.fast_trainer.validate)")
@@ -85,7 +92,8 @@ def main(argv=None):
     if _HERE not in sys.path:
         sys.path.insert(0, _HERE)
     import l3u_plugin
-    l3u_plugin.install(fast_step=True, device_patches=a.device_patches,
+    l3u_plugin.install(fast_step=True,
+                       device_patches="device_draws" if a.device_draws else a.device_patches,
                        fast_validate=a.fast_validate)
     from light_unet.core.config import ConfigManager
     from light_unet.core.trainer import Trainer

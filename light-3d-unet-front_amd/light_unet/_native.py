@@ -88,6 +88,8 @@ _SIGS = {
     "l3u_box_copy": [P, L, I, I, I, P, L, I, I, I, I, I, I, I, I, P],
     "l3u_ccl_nchunks": [L],
     "l3u_aug_patches": [P, I, I, I, I, P, P, P, P, P, P],
+    # the training-patch draws on the device (tables, cfgs: AugTables / AugCfg arrays)
+    "l3u_aug_draw": [P, P, I, D, U64, P, I, I, I, I, P, P, P, P, P],
     "l3u_ccl_label": [P, F, P, P, P, I, I, I, P],
     "l3u_ccl_stats": [P, P, P, P, I, I, I, I, P],
     "l3u_ccl_pairs": [P, P, I, P, L, P],
@@ -176,6 +178,39 @@ class AugParam(ctypes.Structure):
                 ("rot_a1", I), ("rot_c", D), ("rot_s", D), ("rot_off0", D), ("rot_off1", D),
                 ("zoom", I), ("zs", I * 3), ("zst", I * 3), ("zf", D * 3), ("shift_on", I),
                 ("shift", F), ("noise_on", I)]
+
+
+DRAW_MAX_AXES = 8   # L3U_DRAW_MAX_AXES
+
+
+class AugCase(ctypes.Structure):
+    """struct l3u_aug_case (include/l3u.h): one device-resident case volume."""
+    _fields_ = [("image", P), ("label", P), ("sd", I), ("sh", I), ("sw", I), ("pad", I)]
+
+
+class AugTables(ctypes.Structure):
+    """struct l3u_aug_tables: one dataset's device case and location tables."""
+    _fields_ = [("cases", P), ("lesion", P), ("background", P), ("n_lesion", I),
+                ("n_background", I)]
+
+
+class AugCfg(ctypes.Structure):
+    """struct l3u_aug_cfg: lesion_patch_ratio and the augmentation settings."""
+    _fields_ = [("lesion_ratio", D), ("flip_prob", D), ("rot_prob", D), ("scale_prob", D),
+                ("shift_prob", D), ("noise_prob", D), ("rot_lo", D), ("rot_hi", D),
+                ("scale_lo", D), ("scale_hi", D), ("shift_lo", D), ("shift_hi", D),
+                ("noise_sigma", D), ("flip_on", I), ("rot_on", I), ("scale_on", I),
+                ("shift_on", I), ("noise_on", I), ("flip_naxes", I), ("rot_nplanes", I),
+                ("flip_axes", I * DRAW_MAX_AXES), ("rot_planes", (I * 2) * DRAW_MAX_AXES),
+                ("pad", I)]
+
+
+class AugDrawRec(ctypes.Structure):
+    """struct l3u_aug_draw_rec: what l3u_aug_draw drew for one item."""
+    _fields_ = [("domain", I), ("case_idx", I), ("table", I), ("loc", I), ("cz", I), ("cy", I),
+                ("cx", I), ("flip_on", I), ("flip_axis", I), ("rot_on", I), ("rot_a0", I),
+                ("rot_a1", I), ("scale_on", I), ("shift_on", I), ("noise_on", I), ("step", I),
+                ("angle", D), ("scale", D), ("shift", D)]
 
 
 def norm_src_ptr(s):

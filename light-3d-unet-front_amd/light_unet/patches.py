@@ -10,13 +10,26 @@ launch pair of csrc/augment.hip (l3u_aug_patches) cuts and augments a whole batc
 the model's [B, 1, pz, py, px] input.  Given the same RNG state, batch element k is the patch the
 reference's k-th __getitem__ would return (num_workers = 0 semantics), with scipy's float64
 interpolation restated in the kernels (tests/test_patches_gpu.py).
+
+draws="device" is a second draw mode: the same decisions with the same probabilities, made on
+the device by the counter-based generator of include/l3u.h ("Training-patch draws on the device",
+csrc/augdraw.hip l3u_aug_draw) from (draw_seed, a device step counter, item index).  A batch is
+then l3u_aug_draw -> l3u_aug_patches -> l3u_counter_add on persistent buffers: no host RNG call,
+no upload, no allocation and no host sync, and DevicePatchLoader replays that chain as one
+hipGraph.  It is a third patch stream (neither the reference's 16-worker stream nor the
+num_workers = 0 one): the same distribution, different samples.  restate_draws() restates the
+generator in pure Python, so which patch a given (seed, step, item) was can be reproduced
+without a GPU.
 """
+import ctypes
+import math
 import random
 
 import numpy as np
 import torch
 
 from . import _native as nat
+from .engine import _splitmix64, stream_seed
 
 
 class AugDraw:
@@ -108,6 +121,362 @@ def aug_param(img_t, lab_t, center, patch, d):
     return p
 
 
+# ---------------------------------------------------------------- device draws, restated in Python
+# The generator of include/l3u.h ("Training-patch draws on the device"), with Python ints and
+# floats only.  Slot numbers: L3U_DRAW_*.
+_M64 = (1 << 64) - 1
+(SLOT_DOMAIN, SLOT_TABLE, SLOT_LOCATION, SLOT_FLIP_ON, SLOT_FLIP_AXIS, SLOT_ROT_ON, SLOT_ROT_ANGLE,
+ SLOT_ROT_PLANE, SLOT_SCALE_ON, SLOT_SCALE, SLOT_SHIFT_ON, SLOT_SHIFT, SLOT_NOISE_ON, SLOT_NOISE_U1,
+ SLOT_NOISE_U2) = range(15)
+_TWO_PI = 6.283185307179586
+DRAW_MODES = ("host", "device")
+
+
+def draw_key(seed, step, item):
+    """key(seed, step, item) = S(seed ^ S(uint32(step) << 32 | uint32(item)))."""
+    return _splitmix64((int(seed) & _M64) ^
+                       _splitmix64(((int(step) & 0xFFFFFFFF) << 32) | (int(item) & 0xFFFFFFFF)))
+
+
+def draw_bits(key, slot, v=0):
+    """h(slot, v) = S(key ^ S(v << 8 | slot)): the 64 random bits of one draw."""
+    return _splitmix64(key ^ _splitmix64(((int(v) << 8) | int(slot)) & _M64))
+
+
+def _unit(h):
+    return (h >> 11) * 2.0 ** -53          # [0, 1), exact
+
+
+def _choice(h, n):
+    return (h * int(n)) >> 64              # the high 64 bits of the 128-bit product
+
+
+def _range(lo, hi, u):
+    return float(lo) + (float(hi) - float(lo)) * u   # three float64 roundings, as numpy's uniform
+
+
+def aug_settings(aug):
+    """The augmentation config as draw_augmentation reads it (same keys and defaults), flattened:
+    {flip|rot|scale|shift|noise: (enabled, prob, ...)}."""
+    aug = aug or {}
+    f, r = aug.get("random_flip", {}), aug.get("random_rotation", {})
+    s, sh, g = aug.get("random_scale", {}), aug.get("intensity_shift", {}), aug.get("gaussian_noise", {})
+    return {
+        "flip": (bool(f.get("enabled", False)), float(f.get("prob", 0.5)),
+                 [int(a) for a in f.get("axes", [0, 1, 2])]),
+        "rot": (bool(r.get("enabled", False)), float(r.get("prob", 0.5)),
+                [float(v) for v in r.get("angle_range", [-15, 15])],
+                [(int(p[0]), int(p[1])) for p in r.get("axes", [[0, 1], [0, 2], [1, 2]])]),
+        "scale": (bool(s.get("enabled", False)), float(s.get("prob", 0.3)),
+                  [float(v) for v in s.get("scale_range", [0.9, 1.1])]),
+        "shift": (bool(sh.get("enabled", False)), float(sh.get("prob", 0.5)),
+                  [float(v) for v in sh.get("shift_range", [-0.1, 0.1])]),
+        "noise": (bool(g.get("enabled", False)), float(g.get("prob", 0.3)),
+                  float(g.get("sigma", 0.01))),
+    }
+
+
+class DrawSpec:
+    """One dataset as the draws see it: its location lists [(case, (z, y, x)), ...] (lesion,
+    background), lesion_patch_ratio and augmentation config."""
+
+    def __init__(self, lesion, background, lesion_patch_ratio=0.5, augmentation=None):
+        self.lesion = [(int(c), tuple(int(v) for v in zyx)) for c, zyx in lesion]
+        self.background = [(int(c), tuple(int(v) for v in zyx)) for c, zyx in background]
+        self.lesion_patch_ratio = float(lesion_patch_ratio)
+        self.settings = aug_settings(augmentation)
+
+    def __len__(self):
+        return len(self.lesion) + len(self.background)
+
+
+class DrawRecord:
+    """struct l3u_aug_draw_rec: what was drawn for one item (no derived constants)."""
+    FIELDS = ("domain", "case_idx", "table", "loc", "cz", "cy", "cx", "flip_on", "flip_axis",
+              "rot_on", "rot_a0", "rot_a1", "scale_on", "shift_on", "noise_on", "step", "angle",
+              "scale", "shift")
+    __slots__ = FIELDS
+
+    def __init__(self, **kw):
+        for k in self.FIELDS:
+            setattr(self, k, kw[k])
+
+    def astuple(self):
+        return tuple(getattr(self, k) for k in self.FIELDS)
+
+    def __eq__(self, other):
+        return isinstance(other, DrawRecord) and self.astuple() == other.astuple()
+
+    def __repr__(self):
+        return "DrawRecord(" + ", ".join(f"{k}={getattr(self, k)!r}" for k in self.FIELDS) + ")"
+
+    @property
+    def center(self):
+        return (self.cz, self.cy, self.cx)
+
+    def aug_draw(self, noise=None):
+        """The AugDraw of this record (noise: the item's float64 array when noise_on)."""
+        d = AugDraw()
+        d.flip_axis = self.flip_axis if self.flip_on else -1
+        if self.rot_on:
+            d.angle, d.rot_axes = self.angle, (self.rot_a0, self.rot_a1)
+        d.scale = self.scale if self.scale_on else None
+        d.shift = self.shift if self.shift_on else None
+        d.noise = noise if self.noise_on else None
+        return d
+
+
+def restate_draws(seed, step, B, specs, fl_ratio=None):
+    """The DrawRecords l3u_aug_draw writes for a batch of B items at (seed, step), computed from
+    the definition in include/l3u.h with Python ints and floats (no GPU, no numpy RNG).
+    specs: one DrawSpec, or the pair (FL, DLBCL) with fl_ratio for the mixed dataset."""
+    if isinstance(specs, DrawSpec):
+        specs = [specs]
+    specs = list(specs)
+    if len(specs) not in (1, 2) or (len(specs) == 2) != (fl_ratio is not None):
+        raise ValueError("specs: one DrawSpec, or two with fl_ratio")
+    if sum(len(s) for s in specs) == 0 or (len(specs) == 1 and len(specs[0]) == 0):
+        raise ValueError("no locations to draw from")
+    out = []
+    for b in range(int(B)):
+        key = draw_key(seed, step, b)
+
+        def u(slot):
+            return _unit(draw_bits(key, slot))
+        dom = 0
+        if len(specs) == 2:
+            if u(SLOT_DOMAIN) < fl_ratio and len(specs[0]) > 0:
+                dom = 0
+            elif len(specs[1]) > 0:
+                dom = 1
+        sp = specs[dom]
+        if u(SLOT_TABLE) < sp.lesion_patch_ratio and len(sp.lesion) > 0:
+            table = 0
+        elif len(sp.background) > 0:
+            table = 1
+        else:
+            table = 0
+        rows = sp.background if table else sp.lesion
+        loc = _choice(draw_bits(key, SLOT_LOCATION), len(rows))
+        case_idx, (cz, cy, cx) = rows[loc]
+        st = sp.settings
+        r = dict(domain=dom, case_idx=case_idx, table=table, loc=loc, cz=cz, cy=cy, cx=cx,
+                 step=int(step), flip_axis=-1, rot_a0=-1, rot_a1=-1, angle=0.0, scale=0.0, shift=0.0)
+        on, prob, axes = st["flip"]
+        r["flip_on"] = int(on and u(SLOT_FLIP_ON) < prob)
+        if r["flip_on"]:
+            r["flip_axis"] = axes[_choice(draw_bits(key, SLOT_FLIP_AXIS), len(axes))]
+        on, prob, (lo, hi), planes = st["rot"]
+        r["rot_on"] = int(on and u(SLOT_ROT_ON) < prob)
+        if r["rot_on"]:
+            r["angle"] = _range(lo, hi, u(SLOT_ROT_ANGLE))
+            r["rot_a0"], r["rot_a1"] = planes[_choice(draw_bits(key, SLOT_ROT_PLANE), len(planes))]
+        on, prob, (lo, hi) = st["scale"]
+        r["scale_on"] = int(on and u(SLOT_SCALE_ON) < prob)
+        if r["scale_on"]:
+            r["scale"] = _range(lo, hi, u(SLOT_SCALE))
+        on, prob, (lo, hi) = st["shift"]
+        r["shift_on"] = int(on and u(SLOT_SHIFT_ON) < prob)
+        if r["shift_on"]:
+            r["shift"] = _range(lo, hi, u(SLOT_SHIFT))
+        on, prob, _ = st["noise"]
+        r["noise_on"] = int(on and u(SLOT_NOISE_ON) < prob)
+        out.append(DrawRecord(**r))
+    return out
+
+
+def restate_noise(seed, step, item, nvox, sigma):
+    """The item's Box-Muller noise values [nvox] (z-major voxel order) as l3u_aug_draw defines
+    them; libm's log / cos may differ from the device's in the last ulps."""
+    key = draw_key(seed, step, item)
+    out = []
+    for v in range(int(nvox)):
+        u1 = ((draw_bits(key, SLOT_NOISE_U1, v) >> 11) + 1) * 2.0 ** -53      # (0, 1]
+        u2 = _unit(draw_bits(key, SLOT_NOISE_U2, v))
+        out.append(float(sigma) * (math.sqrt(-2.0 * math.log(u1)) * math.cos(_TWO_PI * u2)))
+    return out
+
+
+def _check_mode(draws):
+    if draws not in DRAW_MODES:
+        raise ValueError(f"draws must be one of {DRAW_MODES}, got {draws!r}")
+    return draws
+
+
+def _rank():
+    import torch.distributed as dist
+    return dist.get_rank() if dist.is_available() and dist.is_initialized() else 0
+
+
+def _cfg_struct(spec):
+    """struct l3u_aug_cfg of a DrawSpec."""
+    st, c = spec.settings, nat.AugCfg()
+    c.lesion_ratio = spec.lesion_patch_ratio
+    c.flip_on, c.flip_prob, axes = st["flip"]
+    c.rot_on, c.rot_prob, (c.rot_lo, c.rot_hi), planes = st["rot"]
+    c.scale_on, c.scale_prob, (c.scale_lo, c.scale_hi) = st["scale"]
+    c.shift_on, c.shift_prob, (c.shift_lo, c.shift_hi) = st["shift"]
+    c.noise_on, c.noise_prob, c.noise_sigma = st["noise"]
+    if c.flip_on and not (1 <= len(axes) <= nat.DRAW_MAX_AXES and all(0 <= a <= 2 for a in axes)):
+        raise ValueError(f"random_flip axes {axes}: 1..{nat.DRAW_MAX_AXES} axes out of 0, 1, 2")
+    if c.rot_on and not (1 <= len(planes) <= nat.DRAW_MAX_AXES and
+                         all(0 <= a <= 2 and 0 <= b <= 2 and a != b for a, b in planes)):
+        raise ValueError(f"random_rotation axes {planes}: 1..{nat.DRAW_MAX_AXES} pairs of 0, 1, 2")
+    c.flip_naxes = len(axes) if c.flip_on else 0
+    c.rot_nplanes = len(planes) if c.rot_on else 0
+    for k in range(c.flip_naxes):
+        c.flip_axes[k] = axes[k]
+    for k in range(c.rot_nplanes):
+        c.rot_planes[k][0], c.rot_planes[k][1] = planes[k]
+    return c
+
+
+class _DeviceDraws:
+    """draws="device" state of one DevicePatchDataset (or the two of a DeviceMixedPatchDataset):
+    the device tables, the step and count counters and the persistent per-batch-size buffers,
+    and the launch chain l3u_aug_draw -> l3u_aug_patches -> l3u_counter_add."""
+
+    def __init__(self, datasets, fl_ratio, seed):
+        self.datasets = list(datasets)
+        self.fl_ratio = fl_ratio
+        self.dev, self.patch = self.datasets[0].dev, self.datasets[0].patch_size
+        if any(d.patch_size != self.patch for d in self.datasets):
+            raise ValueError("the two datasets must share one patch size")
+        self.specs = [d.draw_spec() for d in self.datasets]
+        if sum(len(s) for s in self.specs) == 0:
+            raise ValueError("no locations to draw from")
+        self.seed = stream_seed(int(seed) & _M64, _rank())
+        self._keep = []                        # the device tables the structs point into
+        self.tables = (nat.AugTables * len(self.datasets))()
+        self.cfgs = (nat.AugCfg * len(self.datasets))()
+        for k, (ds, sp) in enumerate(zip(self.datasets, self.specs)):
+            self.cfgs[k] = _cfg_struct(sp)
+            cases = (nat.AugCase * max(len(ds.vols), 1))()
+            for i, (img, lab) in enumerate(ds.vols):
+                cases[i].image, cases[i].label = img.data_ptr(), lab.data_ptr()
+                cases[i].sd, cases[i].sh, cases[i].sw = img.shape
+            ct = torch.frombuffer(bytearray(cases), dtype=torch.uint8).to(self.dev)
+            tabs = [self._rows(ds, rows) for rows in (sp.lesion, sp.background)]
+            self._keep += [ct] + tabs
+            t = self.tables[k]
+            t.cases, t.lesion, t.background = ct.data_ptr(), tabs[0].data_ptr(), tabs[1].data_ptr()
+            t.n_lesion, t.n_background = len(sp.lesion), len(sp.background)
+        self.step_t = torch.zeros(1, dtype=torch.int32, device=self.dev)
+        self.counts_t = torch.zeros(2, dtype=torch.int32, device=self.dev)
+        self._bufs, self._graphs, self.last_B = {}, {}, 0
+
+    def _rows(self, ds, rows):
+        """int32 (case, z, y, x) rows on the device; every row is checked against its volume here,
+        once, because the kernels index with them unchecked."""
+        a = np.array([(c, *zyx) for c, zyx in rows], np.int64).reshape(-1, 4)
+        for c, z, y, x in a:
+            if not (0 <= c < len(ds.vols)) or not all(0 <= v < s for v, s in
+                                                     zip((z, y, x), ds.vols[c][0].shape)):
+                raise ValueError(f"location {(c, z, y, x)} lies outside its case volume")
+        if len(a) == 0:                        # a valid pointer for an empty table
+            return torch.zeros(4, dtype=torch.int32, device=self.dev)
+        return torch.from_numpy(a.astype(np.int32)).to(self.dev)
+
+    def buffers(self, B, cut=True):
+        pz, py, px = self.patch
+        P = pz * py * px
+        if B not in self._bufs:
+            self._bufs[B] = {
+                "recs": torch.zeros(B * ctypes.sizeof(nat.AugDrawRec), dtype=torch.uint8, device=self.dev),
+                "prm": torch.zeros(B * ctypes.sizeof(nat.AugParam), dtype=torch.uint8, device=self.dev),
+                "noise": torch.zeros(B, P, dtype=torch.float64, device=self.dev)}
+        buf = self._bufs[B]
+        if cut and "out" not in buf:
+            buf["tmp"] = torch.empty(2, B, P, dtype=torch.float32, device=self.dev)
+            buf["out"] = torch.empty(2, B, 1, pz, py, px, dtype=torch.float32, device=self.dev)
+        return buf
+
+    def launch(self, B, cut=True):
+        """One batch on the current stream (capturable once buffers(B) exists): the draws, the
+        patches (cut=False: draws only) and the counter advance."""
+        buf = self.buffers(B, cut)
+        pz, py, px = self.patch
+        s = nat.stream()
+        nat.call("l3u_aug_draw", self.tables, self.cfgs, len(self.datasets),
+                 float(self.fl_ratio or 0.0), self.seed, self.step_t.data_ptr(), B, pz, py, px,
+                 buf["recs"].data_ptr(), buf["prm"].data_ptr(), buf["noise"].data_ptr(),
+                 self.counts_t.data_ptr(), s)
+        if cut:
+            nat.call("l3u_aug_patches", buf["prm"].data_ptr(), B, pz, py, px, buf["noise"].data_ptr(),
+                     buf["tmp"][0].data_ptr(), buf["tmp"][1].data_ptr(), buf["out"][0].data_ptr(),
+                     buf["out"][1].data_ptr(), s)
+        nat.call("l3u_counter_add", self.step_t.data_ptr(), 1, s)
+        self.last_B = B
+        return (buf["out"][0], buf["out"][1]) if cut else None
+
+    def replay(self, B):
+        """The same batch as launch(B), replayed from a hipGraph captured on first use (a linear
+        chain of five kernel nodes).  The warm-up run leaves no trace on the counters."""
+        g = self._graphs.get(B)
+        if g is None:
+            self.buffers(B)
+            saved = (self.step_t.clone(), self.counts_t.clone())
+            side = torch.cuda.Stream()
+            side.wait_stream(torch.cuda.current_stream())
+            with torch.cuda.stream(side):
+                self.launch(B)
+            torch.cuda.current_stream().wait_stream(side)
+            torch.cuda.synchronize()
+            self.step_t.copy_(saved[0])
+            self.counts_t.copy_(saved[1])
+            torch.cuda.synchronize()
+            g = torch.cuda.CUDAGraph()
+            with torch.cuda.graph(g, capture_error_mode="thread_local"):
+                self.launch(B)
+            self._graphs[B] = g
+        g.replay()
+        self.last_B = B
+        buf = self._bufs[B]
+        return buf["out"][0], buf["out"][1]
+
+    # ---- read-backs (each one synchronises; none is on the per-batch path)
+    def records(self):
+        """The DrawRecords of the last batch, read back from the device."""
+        if not self.last_B:
+            return []
+        raw = self._bufs[self.last_B]["recs"].cpu().numpy().tobytes()
+        arr = (nat.AugDrawRec * self.last_B).from_buffer_copy(raw)
+        return [DrawRecord(**{k: getattr(r, k) for k in DrawRecord.FIELDS}) for r in arr]
+
+    def params(self):
+        """The l3u_aug_param records of the last batch (nat.AugParam array)."""
+        raw = self._bufs[self.last_B]["prm"].cpu().numpy().tobytes()
+        return (nat.AugParam * self.last_B).from_buffer_copy(raw)
+
+    def noise(self):
+        """The last batch's noise buffer [B, pz, py, px] float64 (rows of noise-off items are
+        stale)."""
+        return self._bufs[self.last_B]["noise"].cpu().numpy().reshape(self.last_B, *self.patch)
+
+    def last_draws(self):
+        recs = self.records()
+        nz = self.noise() if any(r.noise_on for r in recs) else None
+        return [(r.case_idx, r.center, r.aug_draw(nz[k] if r.noise_on else None))
+                for k, r in enumerate(recs)]
+
+    def state(self):
+        return self.seed, int(self.step_t.item())
+
+    def set_state(self, state):
+        seed, step = state
+        seed = int(seed) & _M64
+        if seed != self.seed:                  # the seed is a kernel argument of the captured chain
+            self._graphs.clear()
+        self.seed = seed
+        self.step_t.fill_(int(step))
+
+    def take_counts(self):
+        """The per-domain item counts accumulated on the device since the last call (zeroed)."""
+        c = self.counts_t.cpu().tolist()
+        self.counts_t.zero_()
+        return c
+
+
 class DevicePatchDataset:
     """PatchDataset (patch_dataset.py:17-154) over case volumes resident on the device.
 
@@ -115,10 +484,18 @@ class DevicePatchDataset:
     loads per item).  Seeding, location sampling (_sample_locations, :74-100) and the per-item
     draws follow the reference; sample_batch(B) returns device tensors [B, 1, *patch_size].
     from_reference() takes a constructed reference PatchDataset instead: its sampled locations
-    are kept as they are and each case is read once."""
+    are kept as they are and each case is read once.
+
+    draws="device": the per-item draws are made on the device (l3u_aug_draw) from draw_seed
+    (default: `seed`; mixed with the data-parallel rank by engine.stream_seed) and a device step
+    counter; the locations above become device tables once, here.  sample_batch(B) then launches
+    draw -> cut on persistent buffers and returns THOSE buffers (valid until the next batch of the
+    same size; copy what must outlive it), last_draws reads the device records back when
+    accessed, and draw_state() / set_draw_state() expose (seed, step) for a resumed run."""
 
     def __init__(self, cases, patch_size=(48, 48, 48), lesion_patch_ratio=0.5, augmentation=None,
-                 seed=42, device=None, locations=None):
+                 seed=42, device=None, locations=None, draws="host", draw_seed=None):
+        self.draws = _check_mode(draws)
         if not torch.cuda.is_available():
             raise nat.NativeError("DevicePatchDataset needs the ROCm device (no CPU fallback)")
         self.dev = device or torch.device("cuda", torch.cuda.current_device())
@@ -138,16 +515,52 @@ class DevicePatchDataset:
         if locations is None:
             locations = self._sample_locations(cases)
         self.lesion_locations, self.background_locations = locations
-        self.last_draws = []
+        self.seed = seed
+        self._last_draws = []
+        self._dd = None
+        if self.draws == "device":
+            self._dd = _DeviceDraws([self], None, seed if draw_seed is None else draw_seed)
+
+    @property
+    def last_draws(self):
+        """[(case index, centre, AugDraw)] of the last batch (device draws: read back on access)."""
+        return self._dd.last_draws() if self._dd is not None else self._last_draws
+
+    @last_draws.setter
+    def last_draws(self, v):
+        self._last_draws = v
+
+    def draw_spec(self):
+        return DrawSpec(self.lesion_locations, self.background_locations, self.lesion_patch_ratio,
+                        self.augmentation)
+
+    def _device_draws(self):
+        if self._dd is None:
+            raise ValueError('this dataset draws on the host (construct it with draws="device")')
+        return self._dd
+
+    def draw_state(self):
+        """(seed, step) of the device draw stream: the next batch is drawn at `step`."""
+        return self._device_draws().state()
+
+    def set_draw_state(self, state):
+        self._device_draws().set_state(state)
+
+    @property
+    def last_records(self):
+        """The raw DrawRecords of the last batch (device draws)."""
+        return self._device_draws().records()
 
     @classmethod
-    def from_reference(cls, ds, read=None, device=None):
+    def from_reference(cls, ds, read=None, device=None, draws="host", draw_seed=None):
         """The device twin of a constructed reference PatchDataset `ds`: the same cases,
         locations (ds.lesion_locations / background_locations, drawn by its __init__), patch
         size, lesion ratio and augmentation config.  Each case is read ONCE with
         read(path) -> float32 volume (default: `nib.load(path).get_fdata().astype(np.float32)`
         through the nibabel module the reference module imported, patch_dataset.py:129-130)
-        and stays in HBM.  Consumes no random numbers."""
+        and stays in HBM.  Consumes no random numbers.  draws / draw_seed as the constructor's
+        (draw_seed defaults to the reference dataset's seed)."""
+        _check_mode(draws)
         if read is None:
             import sys
             nib = sys.modules[type(ds).__module__].nib
@@ -155,8 +568,10 @@ class DevicePatchDataset:
             def read(path):
                 return nib.load(path).get_fdata().astype(np.float32)
         cases = [(read(c["image_path"]), read(c["label_path"])) for c in ds.cases]
-        return cls(cases, ds.patch_size, ds.lesion_patch_ratio, ds.augmentation, device=device,
-                   locations=(list(ds.lesion_locations), list(ds.background_locations)))
+        return cls(cases, ds.patch_size, ds.lesion_patch_ratio, ds.augmentation,
+                   seed=getattr(ds, "seed", 42), device=device,
+                   locations=(list(ds.lesion_locations), list(ds.background_locations)),
+                   draws=draws, draw_seed=draw_seed)
 
     @staticmethod
     def _sample_locations(cases):
@@ -195,10 +610,22 @@ class DevicePatchDataset:
                                                                       self.patch_size, d)
 
     def sample_batch(self, B):
-        """B consecutive __getitem__ draws, cut and augmented on the device in one launch pair."""
+        """B consecutive __getitem__ draws, cut and augmented on the device in one launch pair
+        (device draws: B items of the next step, drawn on the device too)."""
+        if self._dd is not None:
+            return self._dd.launch(B)
         items = [self.draw_item() for _ in range(B)]
         self.last_draws = [i[0] for i in items]
         return cut_patches(items, self.patch_size, self.dev)
+
+    def replay_batch(self, B):
+        """sample_batch(B) of the device draws as one hipGraph replay (captured on first use)."""
+        return self._device_draws().replay(B)
+
+    def draw_records(self, B):
+        """One step of the device draw stream WITHOUT cutting patches: the B DrawRecords."""
+        self._device_draws().launch(B, cut=False)
+        return self._dd.records()
 
 
 def cut_patches(items, patch, dev):
@@ -231,27 +658,69 @@ class DeviceMixedPatchDataset:
     per-domain sample counts are kept on `counts` (the reference MixedPatchDataset object when
     built by from_reference, so Trainer.train_epoch reads them there, trainer.py:210-256)."""
 
-    def __init__(self, fl, dlbcl, fl_ratio=0.5, counts=None):
+    def __init__(self, fl, dlbcl, fl_ratio=0.5, counts=None, draws="host", draw_seed=None):
+        self.draws = _check_mode(draws)
         self.fl, self.dlbcl, self.fl_ratio = fl, dlbcl, fl_ratio
         self.patch_size, self.dev = fl.patch_size, fl.dev
         self.counts = counts if counts is not None else self
+        self._dd = None
         if counts is None:
             self.reset_sample_counts()
-        self.last_draws = []
+        self._last_draws = []
+        if self.draws == "device":
+            self._dd = _DeviceDraws([fl, dlbcl], float(fl_ratio),
+                                    fl.seed if draw_seed is None else draw_seed)
 
     @classmethod
-    def from_reference(cls, ds, read=None, device=None):
+    def from_reference(cls, ds, read=None, device=None, draws="host", draw_seed=None):
+        _check_mode(draws)
         return cls(DevicePatchDataset.from_reference(ds.fl_dataset, read, device),
                    DevicePatchDataset.from_reference(ds.dlbcl_dataset, read, device),
-                   ds.fl_ratio, counts=ds)
+                   ds.fl_ratio, counts=ds, draws=draws, draw_seed=draw_seed)
+
+    @property
+    def last_draws(self):
+        """[(case index in its domain's dataset, centre, AugDraw)] of the last batch."""
+        return self._dd.last_draws() if self._dd is not None else self._last_draws
+
+    @last_draws.setter
+    def last_draws(self, v):
+        self._last_draws = v
+
+    def _device_draws(self):
+        if self._dd is None:
+            raise ValueError('this dataset draws on the host (construct it with draws="device")')
+        return self._dd
+
+    def draw_state(self):
+        return self._device_draws().state()
+
+    def set_draw_state(self, state):
+        self._device_draws().set_state(state)
+
+    @property
+    def last_records(self):
+        return self._device_draws().records()
+
+    def flush_counts(self):
+        """Device draws: move the item counts accumulated on the device onto `counts` (one
+        device read; DevicePatchLoader calls it once per epoch, after the last batch)."""
+        if self._dd is not None:
+            fl, dl = self._dd.take_counts()
+            self.counts.fl_sample_count += fl
+            self.counts.dlbcl_sample_count += dl
 
     def reset_sample_counts(self):
         self.fl_sample_count = 0
         self.dlbcl_sample_count = 0
+        if self._dd is not None:
+            self._dd.counts_t.zero_()
 
     def get_sample_counts(self):
-        return {"fl_samples": self.fl_sample_count, "dlbcl_samples": self.dlbcl_sample_count,
-                "total_samples": self.fl_sample_count + self.dlbcl_sample_count}
+        self.flush_counts()
+        c = self.counts
+        return {"fl_samples": c.fl_sample_count, "dlbcl_samples": c.dlbcl_sample_count,
+                "total_samples": c.fl_sample_count + c.dlbcl_sample_count}
 
     def __len__(self):
         return len(self.fl) + len(self.dlbcl)
@@ -269,9 +738,18 @@ class DeviceMixedPatchDataset:
         return self.fl.draw_item()
 
     def sample_batch(self, B):
+        if self._dd is not None:
+            return self._dd.launch(B)
         items = [self.draw_item() for _ in range(B)]
         self.last_draws = [i[0] for i in items]
         return cut_patches(items, self.patch_size, self.dev)
+
+    def replay_batch(self, B):
+        return self._device_draws().replay(B)
+
+    def draw_records(self, B):
+        self._device_draws().launch(B, cut=False)
+        return self._dd.records()
 
 
 class DevicePatchLoader:
@@ -282,7 +760,14 @@ class DevicePatchLoader:
     is ragged, and each epoch takes the two int64 seeds a torch DataLoader iterator draws from
     torch's global generator (the iterator's base seed and RandomSampler's seed), so the torch
     RNG stream after an epoch is the host loader's.  Batches are device tensors
-    (images, labels) [b, 1, *patch_size]."""
+    (images, labels) [b, 1, *patch_size].
+
+    Over a draws="device" dataset the batches are the device stream's instead (the global numpy /
+    python RNGs are not touched): every full batch is one replay of the dataset's captured
+    draw -> cut -> counter chain (captured once per batch size), the ragged last batch runs the
+    same chain eagerly, and the batch tensors are the dataset's persistent buffers (consume a
+    batch before asking for the next).  The mixed dataset's domain counts are moved from the
+    device onto its `counts` object once, after the last batch."""
 
     def __init__(self, dataset, batch_size):
         self.dataset, self.batch_size = dataset, int(batch_size)
@@ -294,15 +779,24 @@ class DevicePatchLoader:
         torch.empty((), dtype=torch.int64).random_()   # _BaseDataLoaderIter._base_seed
         torch.empty((), dtype=torch.int64).random_()   # RandomSampler's generator seed
         n = len(self.dataset)
+        device = getattr(self.dataset, "draws", "host") == "device"
         for b0 in range(0, n, self.batch_size):
-            yield self.dataset.sample_batch(min(self.batch_size, n - b0))
+            b = min(self.batch_size, n - b0)
+            if device and b == self.batch_size:
+                yield self.dataset.replay_batch(b)
+            else:
+                yield self.dataset.sample_batch(b)
+        if device and hasattr(self.dataset, "flush_counts"):
+            self.dataset.flush_counts()
 
 
-def device_loader(dataset, batch_size, read=None, device=None):
+def device_loader(dataset, batch_size, read=None, device=None, draws="host", draw_seed=None):
     """A DevicePatchLoader for a reference PatchDataset / MixedPatchDataset (by duck type:
-    MixedPatchDataset carries fl_dataset / dlbcl_dataset)."""
+    MixedPatchDataset carries fl_dataset / dlbcl_dataset).  draws="device": the device draw
+    stream (draw_seed defaults to the reference dataset's seed)."""
+    _check_mode(draws)
     if hasattr(dataset, "fl_dataset") and hasattr(dataset, "dlbcl_dataset"):
-        dd = DeviceMixedPatchDataset.from_reference(dataset, read, device)
+        dd = DeviceMixedPatchDataset.from_reference(dataset, read, device, draws, draw_seed)
     else:
-        dd = DevicePatchDataset.from_reference(dataset, read, device)
+        dd = DevicePatchDataset.from_reference(dataset, read, device, draws, draw_seed)
     return DevicePatchLoader(dd, batch_size)
