@@ -956,6 +956,35 @@ int l3u_pp_morph(const unsigned long long* in, unsigned long long* out, int erod
 int l3u_pp_mask_stats(const unsigned long long* bits, long long* stats, int D, int H, int W,
                       hipStream_t stream);
 
+/* ---- patch locations (csrc/locate.hip; PatchDataset._sample_locations,
+ * light_unet/datasets/patch_dataset.py:74-100) ----
+ * The reference keeps rows of np.argwhere(label > 0) and of np.argwhere((label == 0) & body_mask)
+ * picked by np.random.randint; row k of np.argwhere(m) is the k-th set voxel of m in C order, so
+ * the kept rows are rank queries over a predicate that is never materialised.  Over the flat index
+ * i = (z * H + y) * W + x of a [D, H, W] volume the two voxel classes are
+ *   class 0 (lesion):      label[i] > 0
+ *   class 1 (background):  label[i] == 0 && (body == NULL || body[i] != 0)
+ * evaluated in the label's own type (label_dtype 0 float, 1 double, as l3u_pp_pack's codes; a NaN
+ * or a negative label belongs to neither class); body is one byte per voxel (bool / uint8).
+ *
+ * l3u_loc_count: prefix[2][nblocks + 1] uint32, nblocks = l3u_loc_nblocks(n): per class the
+ * EXCLUSIVE prefix sum of the per-block voxel counts (blocks of L3U_LOC_BLOCK voxels of the flat
+ * order), entry nblocks the class total.  Integer sums in a fixed order: no atomics.
+ * n = D * H * W with 0 < n < 2^31, else hipErrorInvalidValue before any launch.
+ *
+ * l3u_loc_select: rows[r] = (case_idx, z, y, x) of the ranks[r]-th voxel (0-based, C order) of
+ * class cls, from the prefix l3u_loc_count wrote for the same label / body; a rank outside
+ * [0, total) gives (case_idx, -1, -1, -1) and reads nothing out of range.  ranks: int64 device
+ * memory; rows: int32 [R][4], 16-byte aligned; R >= 0 (R == 0: no launch, success).  Workspace is
+ * the prefix alone: 8 bytes per L3U_LOC_BLOCK voxels. */
+#define L3U_LOC_BLOCK 4096
+int l3u_loc_nblocks(long long n);
+int l3u_loc_count(const void* label, int label_dtype, const unsigned char* body, long long n,
+                  unsigned int* prefix, hipStream_t stream);
+int l3u_loc_select(const void* label, int label_dtype, const unsigned char* body, int D, int H,
+                   int W, const unsigned int* prefix, int cls, const long long* ranks, int R,
+                   int case_idx, int* rows, hipStream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

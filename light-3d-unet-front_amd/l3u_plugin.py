@@ -137,7 +137,18 @@ def _bind_device_patches(done, draws="host"):
     done["light_unet.datasets.loader"] = ["_create_train_loader"]
 
 
-def install(fast_step=False, lesion=True, device_patches=False, fast_validate=False):
+def _bind_device_locations(done):
+    """PatchDataset._sample_locations (patch_dataset.py:74-100) on the device
+    (l3u_amd.patches.bind_sample_locations): the case labels and body masks read as the reference
+    reads them, the voxel counts and the rank-select on the device, the reference's randint calls
+    on the host.  The same lists; the original stays on PatchDataset._l3u_reference_sample_locations."""
+    pd = importlib.import_module("light_unet.datasets.patch_dataset")
+    sys.modules[ALIAS + ".patches"].bind_sample_locations(pd.PatchDataset)
+    done.setdefault("light_unet.datasets.patch_dataset", []).append("PatchDataset._sample_locations")
+
+
+def install(fast_step=False, lesion=True, device_patches=False, fast_validate=False,
+            device_locations=False):
     """Bind this build's model and loss into the already-importable reference package.
     Returns {module: [names]} of what was replaced.  Raises ImportError when the reference's
     light_unet.models.{unet3d,losses} cannot be imported (nothing is half-installed).
@@ -166,8 +177,19 @@ def install(fast_step=False, lesion=True, device_patches=False, fast_validate=Fa
     the metrics, the captured network forward is reused across cases and epochs, and every
     threshold of threshold_sensitivity_range is evaluated from one level-batched labelling per
     case (lesion.sweep_metrics).  Same return value; the original stays reachable as
-    Trainer._l3u_reference_validate.  Needs light_unet.core.trainer."""
+    Trainer._l3u_reference_validate.  Needs light_unet.core.trainer.
 
+    device_locations=True also replaces PatchDataset._sample_locations (patch_dataset.py:74-100):
+    every case's label and body mask are read as the reference reads them and uploaded (label as
+    float64), the lesion / background voxels are counted on the device, the reference's randint
+    calls are made on those counts and the drawn rows come from a rank-select on the device
+    (l3u_loc_count / l3u_loc_select) instead of np.argwhere lists on the host.  The same two
+    lists and the same numpy generator state; the original stays reachable as
+    PatchDataset._l3u_reference_sample_locations.  Needs light_unet.datasets.patch_dataset (and
+    its NIfTI reader).  Any value but True / False raises ValueError."""
+
+    if device_locations is not True and device_locations is not False:
+        raise ValueError(f"device_locations must be True or False, got {device_locations!r}")
     if isinstance(device_patches, str) and device_patches != "device_draws":
         raise ValueError(f"device_patches must be one of {DEVICE_PATCHES}, got {device_patches!r}")
     amd = load()
@@ -202,6 +224,8 @@ def install(fast_step=False, lesion=True, device_patches=False, fast_validate=Fa
         done.setdefault("light_unet.core.trainer", []).append("Trainer.validate")
     if device_patches:
         _bind_device_patches(done, "device" if device_patches == "device_draws" else "host")
+    if device_locations:
+        _bind_device_locations(done)
     if lesion:
         _bind_lesion(done)
     amd.installed_into = done

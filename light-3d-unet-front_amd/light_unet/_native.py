@@ -132,6 +132,10 @@ _SIGS = {
     "l3u_pp_morph_max_iters": [I],
     "l3u_pp_morph": [P, P, I, I, I, I, I, P],
     "l3u_pp_mask_stats": [P, P, I, I, I, P],
+    # patch locations: per-block class counts + prefix, rank-select of (case, z, y, x) rows
+    "l3u_loc_nblocks": [L],
+    "l3u_loc_count": [P, I, P, L, P, P],
+    "l3u_loc_select": [P, I, P, I, I, I, P, I, P, I, I, P, P],
 }
 # entry points with a _bf16 twin (same arguments; saved activations stored as bf16, gradients
 # fp32, include/l3u.h)
@@ -155,7 +159,10 @@ _QUERIES = {"l3u_abi_version", "l3u_dw3_nchunk", "l3u_pw_stat_nsb", "l3u_pw_bwd_
             "l3u_gconv3_nblocks", "l3u_gconv3_wgrad_nparts", "l3u_front_nblocks",
             "l3u_ccl_nchunks", "l3u_dwpw_supported", "l3u_dwpw_stat_nsb",
             "l3u_dw3_bwd_rank1", "l3u_pw_bwd2_supported", "l3u_pw_bwd_chunk",
-            "l3u_ccl_lv_max_levels", "l3u_pp_select_ws_bytes", "l3u_pp_morph_max_iters"}
+            "l3u_ccl_lv_max_levels", "l3u_pp_select_ws_bytes", "l3u_pp_morph_max_iters",
+            "l3u_loc_nblocks"}
+
+LOC_BLOCK = 4096    # L3U_LOC_BLOCK
 
 _lib = None
 

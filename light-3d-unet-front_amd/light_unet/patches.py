@@ -20,6 +20,10 @@ hipGraph.  It is a third patch stream (neither the reference's 16-worker stream 
 num_workers = 0 one): the same distribution, different samples.  restate_draws() restates the
 generator in pure Python, so which patch a given (seed, step, item) was can be reproduced
 without a GPU.
+
+locate="device" moves _sample_locations (patch_dataset.py:74-100) off the host's voxels: the
+reference's randint calls are made on voxel counts from l3u_loc_count and the drawn rows come
+from l3u_loc_select (csrc/locate.hip), the same lists as the host pass with ==.
 """
 import ctypes
 import math
@@ -303,6 +307,165 @@ def _check_mode(draws):
     return draws
 
 
+# ---------------------------------------------------------------- patch locations on the device
+# PatchDataset._sample_locations (patch_dataset.py:74-100) without its host pass over the voxels:
+# row k of np.argwhere(m) is the k-th set voxel of m in C order, so the rows the reference keeps
+# are rank queries (csrc/locate.hip: l3u_loc_count / l3u_loc_select).
+LOCATE_MODES = ("host", "device")
+_LOC_DTYPES = {torch.float32: 0, torch.float64: 1}
+_NP_OF = {torch.float32: np.float32, torch.float64: np.float64, torch.bool: np.bool_}
+
+
+def _check_locate(locate):
+    if locate not in LOCATE_MODES:
+        raise ValueError(f"locate must be one of {LOCATE_MODES}, got {locate!r}")
+    return locate
+
+
+def _loc_inputs(vols, body_masks):
+    """[(label, body or None)]: contiguous device tensors, float32 / float64 labels and one-byte
+    masks of the label's shape.  vols: label volumes, or (image, label) pairs."""
+    labels = [v[1] if isinstance(v, (tuple, list)) else v for v in vols]
+    if body_masks is None:
+        body_masks = [None] * len(labels)
+    if len(body_masks) != len(labels):
+        raise ValueError("one body mask (or None) per case")
+    out = []
+    for lab, body in zip(labels, body_masks):
+        if not torch.is_tensor(lab) or not lab.is_cuda or lab.dtype not in _LOC_DTYPES:
+            raise nat.NativeError("locations on the device need float32 / float64 ROCm device "
+                                  "labels; there is no CPU fallback")
+        if lab.ndim != 3 or lab.numel() == 0 or lab.numel() >= 2 ** 31:
+            raise ValueError("a label must be a 3D volume of 1 .. 2^31 - 1 voxels")
+        if body is not None:
+            if not torch.is_tensor(body) or body.device != lab.device or \
+                    body.dtype not in (torch.bool, torch.uint8):
+                raise nat.NativeError("a body mask must be a torch.bool / uint8 tensor on the "
+                                      "label's device")
+            if body.shape != lab.shape:
+                raise ValueError("a body mask must have its label's shape")
+            body = body.contiguous()
+        out.append((lab.contiguous(), body))
+    return out
+
+
+def _loc_count_launch(inputs):
+    """l3u_loc_count of every case on the current stream, no sync: (one int32 workspace holding
+    every case's uint32 prefix [2][nblocks + 1], the cases' offsets into it, their block counts)."""
+    nbs = [nat.query("l3u_loc_nblocks", lab.numel()) for lab, _ in inputs]
+    offs = [0]
+    for nb in nbs:
+        offs.append(offs[-1] + 2 * (nb + 1))
+    dev = inputs[0][0].device if inputs else None
+    ws = torch.empty(max(offs[-1], 1), dtype=torch.int32, device=dev)
+    s = nat.stream()
+    for (lab, body), off in zip(inputs, offs):
+        nat.call("l3u_loc_count", lab.data_ptr(), _LOC_DTYPES[lab.dtype], nat.ptr(body),
+                 lab.numel(), nat.ptr(ws, off), s)
+    return ws, offs, nbs
+
+
+def _loc_totals(ws, offs, nbs):
+    """int64 [ncases, 2] (lesion, background) voxel counts: ONE read-back for all cases."""
+    if not nbs:
+        return np.zeros((0, 2), np.int64)
+    idx = [o + c * (nb + 1) + nb for o, nb in zip(offs, nbs) for c in (0, 1)]
+    return torch.stack([ws[i] for i in idx]).cpu().numpy().astype(np.int64).reshape(-1, 2)
+
+
+def location_counts(vols, body_masks=None):
+    """The number of lesion voxels (label > 0) and of background voxels (label == 0, inside the
+    body mask where one is given) of every case: int64 [ncases, 2].  vols: device label volumes
+    (float32 / float64; or (image, label) pairs), body_masks: per case None or a torch.bool /
+    uint8 device tensor.  The counts of all cases are launched without a sync in between and
+    read back once."""
+    return _loc_totals(*_loc_count_launch(_loc_inputs(vols, body_masks)))
+
+
+def draw_location_ranks(counts, rng=np.random):
+    """_sample_locations' random draws (patch_dataset.py:83-98) from the per-case voxel counts
+    [(n_lesion, n_background)]: per case rng.randint(n_les, size=max(10, n_les // 1000)) only if
+    n_les > 0, then rng.randint(n_bg, size=max(10, n_bg // 5000)) only if n_bg > 0 -- the
+    reference's calls in the reference's order, so the generator ends in the reference's state.
+    Returns per case (lesion ranks, background ranks): indices into np.argwhere's rows, i.e.
+    0-based C-order ranks among the class's voxels (empty int64 arrays where nothing is drawn).
+    No GPU use."""
+    out = []
+    for n_les, n_bg in counts:
+        n_les, n_bg = int(n_les), int(n_bg)
+        les = bg = np.zeros(0, np.int64)
+        if n_les > 0:
+            les = np.asarray(rng.randint(n_les, size=max(10, n_les // 1000)), np.int64)
+        if n_bg > 0:
+            bg = np.asarray(rng.randint(n_bg, size=max(10, n_bg // 5000)), np.int64)
+        out.append((les, bg))
+    return out
+
+
+def sample_locations_device(vols, body_masks=None, rng=np.random):
+    """_sample_locations (patch_dataset.py:74-100) on device-resident cases: counts (one
+    read-back) -> draw_location_ranks on the host -> one upload of all ranks -> the select
+    launches.  Returns two int32 [n, 4] device tables of (case index, z, y, x) rows, lesion and
+    background, in the reference's row order (per case, in draw order): the rows the reference's
+    lists hold, given the same generator state.  Arguments as location_counts."""
+    inputs = _loc_inputs(vols, body_masks)
+    ws, offs, nbs = _loc_count_launch(inputs)
+    ranks = draw_location_ranks(_loc_totals(ws, offs, nbs), rng)
+    dev = inputs[0][0].device if inputs else torch.device("cuda", torch.cuda.current_device())
+    flat = np.concatenate([r for pair in ranks for r in pair] + [np.zeros(1, np.int64)])
+    ranks_t = torch.from_numpy(flat).to(dev)
+    tabs = [torch.empty(max(sum(len(p[c]) for p in ranks), 1), 4, dtype=torch.int32, device=dev)
+            for c in (0, 1)]
+    s = nat.stream()
+    at, row = 0, [0, 0]
+    for ci, ((lab, body), off, pair) in enumerate(zip(inputs, offs, ranks)):
+        for c in (0, 1):
+            R = len(pair[c])
+            nat.call("l3u_loc_select", lab.data_ptr(), _LOC_DTYPES[lab.dtype], nat.ptr(body),
+                     *lab.shape, nat.ptr(ws, off), c, nat.ptr(ranks_t, at), R, ci,
+                     nat.ptr(tabs[c], 4 * row[c]), s)
+            at += R
+            row[c] += R
+    return tabs[0][:row[0]], tabs[1][:row[1]]
+
+
+def _rows_to_locations(rows):
+    """An int [n, 4] table as the reference's list [(case index, np.int64 [z, y, x])]."""
+    return [(int(r[0]), np.array(r[1:], np.int64)) for r in np.asarray(rows)]
+
+
+def bind_sample_locations(PatchDataset):
+    """Replace PatchDataset._sample_locations (patch_dataset.py:74-100) with the device form.
+    Each case's label and body mask are read exactly as the reference reads them
+    (`nib.load(case["label_path"]).get_fdata()` through the nibabel module PatchDataset's own
+    module imported, and self._load_body_mask_array(case)), uploaded with the label as float64
+    (so the predicate is the reference's), and the rows are selected on the device with the
+    reference's randint calls: the same two lists, the same numpy generator state afterwards.
+    All labels of the dataset are in HBM at once (8 bytes per voxel) until the method returns.
+    The original stays reachable as PatchDataset._l3u_reference_sample_locations."""
+    import sys
+    mod = sys.modules[PatchDataset.__module__]
+    if not hasattr(PatchDataset, "_l3u_reference_sample_locations"):
+        PatchDataset._l3u_reference_sample_locations = PatchDataset._sample_locations
+
+    def _sample_locations(self):
+        if not torch.cuda.is_available():
+            raise nat.NativeError("device locations need the ROCm device (no CPU fallback)")
+        dev = torch.device("cuda", torch.cuda.current_device())
+        labels, bodies = [], []
+        for case in self.cases:
+            label = np.asarray(mod.nib.load(case["label_path"]).get_fdata(), np.float64)
+            body = self._load_body_mask_array(case)
+            labels.append(torch.from_numpy(np.ascontiguousarray(label)).to(dev))
+            bodies.append(None if body is None else
+                          torch.from_numpy(np.ascontiguousarray(np.asarray(body).astype(bool))).to(dev))
+        les, bg = sample_locations_device(labels, bodies)
+        both = torch.cat([les, bg]).cpu().numpy()
+        return _rows_to_locations(both[:len(les)]), _rows_to_locations(both[len(les):])
+    PatchDataset._sample_locations = _sample_locations
+    return _sample_locations
+
+
 def _rank():
     import torch.distributed as dist
     return dist.get_rank() if dist.is_available() and dist.is_initialized() else 0
@@ -356,7 +519,13 @@ class _DeviceDraws:
                 cases[i].image, cases[i].label = img.data_ptr(), lab.data_ptr()
                 cases[i].sd, cases[i].sh, cases[i].sw = img.shape
             ct = torch.frombuffer(bytearray(cases), dtype=torch.uint8).to(self.dev)
-            tabs = [self._rows(ds, rows) for rows in (sp.lesion, sp.background)]
+            if getattr(ds, "location_tables", None) is not None:
+                # selected on the device from the case volumes themselves: in range by
+                # construction, already in HBM (an empty table still needs a valid pointer)
+                tabs = [t if len(t) else torch.zeros(4, dtype=torch.int32, device=self.dev)
+                        for t in ds.location_tables]
+            else:
+                tabs = [self._rows(ds, rows) for rows in (sp.lesion, sp.background)]
             self._keep += [ct] + tabs
             t = self.tables[k]
             t.cases, t.lesion, t.background = ct.data_ptr(), tabs[0].data_ptr(), tabs[1].data_ptr()
@@ -491,11 +660,22 @@ class DevicePatchDataset:
     counter; the locations above become device tables once, here.  sample_batch(B) then launches
     draw -> cut on persistent buffers and returns THOSE buffers (valid until the next batch of the
     same size; copy what must outlive it), last_draws reads the device records back when
-    accessed, and draw_state() / set_draw_state() expose (seed, step) for a resumed run."""
+    accessed, and draw_state() / set_draw_state() expose (seed, step) for a resumed run.
+
+    locate="device": _sample_locations runs on the device (sample_locations_device: the
+    reference's randint calls on voxel counts, the rows by rank-select, no np.argwhere).  The
+    cases may then be numpy arrays or device tensors, the optional third element a numpy bool /
+    uint8 mask or a torch.bool / uint8 device tensor -- what preprocess_volume(output="device")
+    returns; labels are tested in the float32 the dataset holds.  The device tables stay on
+    `location_tables` (draws="device" uses them as they are); lesion_locations /
+    background_locations are the same rows read back once.  Same lists and the same numpy
+    generator state as locate="host"."""
 
     def __init__(self, cases, patch_size=(48, 48, 48), lesion_patch_ratio=0.5, augmentation=None,
-                 seed=42, device=None, locations=None, draws="host", draw_seed=None):
+                 seed=42, device=None, locations=None, draws="host", draw_seed=None, locate="host"):
         self.draws = _check_mode(draws)
+        self.locate = _check_locate(locate)
+        self.location_tables = None
         if not torch.cuda.is_available():
             raise nat.NativeError("DevicePatchDataset needs the ROCm device (no CPU fallback)")
         self.dev = device or torch.device("cuda", torch.cuda.current_device())
@@ -506,14 +686,17 @@ class DevicePatchDataset:
             random.seed(seed)
             np.random.seed(seed)
         self.vols = []
-        for case in cases:
-            img, lab = np.asarray(case[0], np.float32), np.asarray(case[1], np.float32)
-            if img.shape != lab.shape or img.ndim != 3:
-                raise ValueError("image and label must be matching 3D volumes")
-            self.vols.append((torch.from_numpy(np.ascontiguousarray(img)).to(self.dev),
-                              torch.from_numpy(np.ascontiguousarray(lab)).to(self.dev)))
-        if locations is None:
-            locations = self._sample_locations(cases)
+        if self.locate == "device":
+            locations = self._upload_and_locate(cases, locations)
+        else:
+            for case in cases:
+                img, lab = np.asarray(case[0], np.float32), np.asarray(case[1], np.float32)
+                if img.shape != lab.shape or img.ndim != 3:
+                    raise ValueError("image and label must be matching 3D volumes")
+                self.vols.append((torch.from_numpy(np.ascontiguousarray(img)).to(self.dev),
+                                  torch.from_numpy(np.ascontiguousarray(lab)).to(self.dev)))
+            if locations is None:
+                locations = self._sample_locations(cases)
         self.lesion_locations, self.background_locations = locations
         self.seed = seed
         self._last_draws = []
@@ -572,6 +755,35 @@ class DevicePatchDataset:
                    seed=getattr(ds, "seed", 42), device=device,
                    locations=(list(ds.lesion_locations), list(ds.background_locations)),
                    draws=draws, draw_seed=draw_seed)
+
+    def _to_dev(self, a, dtype):
+        if torch.is_tensor(a):
+            return a.to(device=self.dev, dtype=dtype).contiguous()
+        return torch.from_numpy(np.ascontiguousarray(np.asarray(a, dtype=_NP_OF[dtype]))).to(self.dev)
+
+    def _upload_and_locate(self, cases, locations):
+        """locate="device": the cases (numpy arrays or device tensors, float32 in HBM) and, unless
+        `locations` is given, their locations by sample_locations_device over the float32 labels:
+        the device tables stay on `location_tables`, the lists are the same rows read back once."""
+        bodies = []
+        for case in cases:
+            img, lab = self._to_dev(case[0], torch.float32), self._to_dev(case[1], torch.float32)
+            if img.shape != lab.shape or img.ndim != 3:
+                raise ValueError("image and label must be matching 3D volumes")
+            body = case[2] if len(case) > 2 else None
+            if body is not None:
+                if torch.is_tensor(body) and body.dtype == torch.uint8:
+                    body = body.to(self.dev).contiguous()
+                else:                          # numpy: .astype(bool), as _load_body_mask_array
+                    body = self._to_dev(body, torch.bool)
+            self.vols.append((img, lab))
+            bodies.append(body)
+        if locations is not None:
+            return locations
+        les, bg = sample_locations_device([lab for _, lab in self.vols], bodies)
+        self.location_tables = (les, bg)
+        both = torch.cat([les, bg]).cpu().numpy()
+        return _rows_to_locations(both[:len(les)]), _rows_to_locations(both[len(les):])
 
     @staticmethod
     def _sample_locations(cases):
