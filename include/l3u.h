@@ -40,7 +40,9 @@ typedef unsigned short l3u_bf16;   /* bfloat16 bit pattern (torch.bfloat16 stora
 
 /* ABI version of this header (L3U_ABI_VERSION); the ctypes binding refuses a library that reports
  * another.  3: l3u_norm_src.rank1, L3U_ADAMW_TICKET_INTS tickets, the l3u_sblock_* entry points
- * removed (round 3); the round-4 entry points.  5: l3u_pw_bwd_chunk (round 6). */
+ * removed (round 3); the round-4 entry points.  5: l3u_pw_bwd_chunk (round 6).  Added since
+ * without a new version (additive, nothing existing changed): l3u_window_occupancy,
+ * l3u_window_blend_masked. */
 #define L3U_ABI_VERSION 5
 int l3u_abi_version(void);
 
@@ -720,6 +722,28 @@ int l3u_window_gather(const float* img, int D, int H, int W, const int* pos, int
 int l3u_window_blend(const float* preds, const int* zpos, int nz, const int* ypos, int ny,
                      const int* xpos, int nx, const float* imp, int D, int H, int W, int pd, int ph,
                      int pw, float* prob, hipStream_t stream);
+
+/* The same map times a body mask (prob_map * body_mask, trainer.py:401-402, inferencer.py:161-162)
+ * without the forwards of windows that lie outside the mask.  mask: [D][H][W] of mask_dtype 0
+ * float or 2 uint8 (l3u_pp_pack's codes); anything else returns hipErrorInvalidValue.
+ * occupancy:    keep[(iz*ny + iy)*nx + ix] = 1 if some voxel of that grid window's box, clipped to
+ *               the volume, has mask != 0 (a NaN counts as nonzero), else 0; one workgroup per
+ *               window, no atomics
+ * blend_masked: l3u_window_blend over a compact prediction buffer: window (iz, iy, ix) is row
+ *               slot[(iz*ny + iy)*nx + ix] of preds, -1 where it was not computed.  A voxel with
+ *               mask == 0 is stored as +0 and reads no prediction; every other voxel is accumulated
+ *               as l3u_window_blend does (same window order, separate fp32 multiply / add / divide)
+ *               and stored as that quotient times float(mask).  Every window covering a voxel with
+ *               mask != 0 must have a row (occupancy keeps all of them); a covering window with a
+ *               negative slot is left out of the sums, never indexed.  For finite predictions the
+ *               result is bit for bit l3u_window_blend's map times the mask in float32.          */
+int l3u_window_occupancy(const void* mask, int mask_dtype, int D, int H, int W, const int* zpos,
+                         int nz, const int* ypos, int ny, const int* xpos, int nx, int pd, int ph,
+                         int pw, int* keep, hipStream_t stream);
+int l3u_window_blend_masked(const float* preds, const int* slot, const int* zpos, int nz,
+                            const int* ypos, int ny, const int* xpos, int nx, const float* imp,
+                            const void* mask, int mask_dtype, int D, int H, int W, int pd, int ph,
+                            int pw, float* prob, hipStream_t stream);
 
 /* storage casts (the bf16 network's input / input gradient); n elements                      */
 int l3u_cast_f32_bf16(const float* x, l3u_bf16* y, long long n, hipStream_t stream);

@@ -8,6 +8,10 @@
 //                  where count > 0 (utils.py:135) -- the same float32 operation sequence as the
 //                  reference's numpy accumulation, done by one thread per voxel (deterministic:
 //                  no atomics, no order dependence on the batching)
+//   window_occupancy / window_blend_masked  the same map times a body mask (trainer.py:401-402,
+//                  inferencer.py:161-162) without the forwards of windows the mask empties: which
+//                  windows hold a nonzero mask voxel, and the blend over a compact prediction
+//                  buffer that stores +0 wherever the mask is 0
 #include "common.h"
 using namespace l3u;
 
@@ -65,6 +69,101 @@ __global__ __launch_bounds__(256) void window_blend_kernel(
   }
 }
 
+// ---- windows outside the body mask ---------------------------------------------------------------
+// 16-byte units of the mask element types (float32 / uint8) and "some element is nonzero" on one.
+// A float compares as a float: -0.0 is zero, a NaN is not.
+typedef unsigned int u4_t __attribute__((ext_vector_type(4)));
+L3U_DEV bool nz1(float v) { return v != 0.f; }
+L3U_DEV bool nz1(unsigned char v) { return v != 0; }
+L3U_DEV bool nz16(const float* p) {
+  const f4_t v = ldv4(p);
+  return v[0] != 0.f || v[1] != 0.f || v[2] != 0.f || v[3] != 0.f;
+}
+L3U_DEV bool nz16(const unsigned char* p) {
+  const u4_t v = *reinterpret_cast<const u4_t*>(p);
+  return (v[0] | v[1] | v[2] | v[3]) != 0u;
+}
+
+// One workgroup per grid window: keep[win] = 1 iff the window's box, clipped to the volume, holds
+// a nonzero mask element.  A row of the box is read in the 16-byte units of the address space (a
+// unit that lies inside the row as one vector load, the ragged ends element by element), so rows
+// of any alignment take wide loads in their middle.  Work item i = (row, unit); a thread stops at
+// its first hit, the workgroup ORs the flags and thread 0 stores the word.  A thread's next load
+// waits for the test of its last one, so an empty window (the only kind that is read to the end)
+// costs one memory latency per sweep of the workgroup: 1024 threads keep 4x the loads of a
+// 256-thread workgroup in flight (48^3 float window: 30 sweeps).
+constexpr int kOccThreads = 1024;
+template <typename M>
+__global__ __launch_bounds__(kOccThreads) void window_occupancy_kernel(
+    const M* __restrict__ mask, int D, int H, int W, const int* __restrict__ zp,
+    const int* __restrict__ yp, int ny, const int* __restrict__ xp, int nx, int pd, int ph, int pw,
+    int* __restrict__ keep) {
+  constexpr int E = 16 / (int)sizeof(M);   // elements per unit
+  const int win = blockIdx.x;
+  const int ix = win % nx, t = win / nx, iy = t % ny, iz = t / ny;
+  const int z0 = max(zp[iz], 0), y0 = max(yp[iy], 0), x0 = max(xp[ix], 0);
+  const int z1 = min(zp[iz] + pd, D), y1 = min(yp[iy] + ph, H), x1 = min(xp[ix] + pw, W);
+  const int cd = z1 - z0, ch = y1 - y0, cw = x1 - x0;
+  int found = 0;
+  if (cd > 0 && ch > 0 && cw > 0) {
+    const int U = (cw + E - 1) / E + 1;   // units a row of cw elements can touch
+    const long long items = (long long)cd * ch * U;
+    for (long long i = threadIdx.x; i < items && !found; i += kOccThreads) {
+      const int u = (int)(i % U), r = (int)(i / U), y = y0 + r % ch, z = z0 + r / ch;
+      const M* row = mask + ((long long)z * H + y) * W + x0;
+      // element offset (from the row's start) of the row's first 16-byte boundary, then unit u
+      const int head = (int)((E - (int)(((uintptr_t)row / sizeof(M)) % E)) % E);
+      const int lo = head - E + u * E, hi = lo + E;   // unit u = elements [lo, hi) of the row
+      if (lo >= cw || hi <= 0) continue;
+      if (lo >= 0 && hi <= cw && ((uintptr_t)(row + lo) & 15) == 0) {
+        found = nz16(row + lo);
+      } else {
+        for (int k = max(lo, 0); k < min(hi, cw); ++k) found |= nz1(row[k]) ? 1 : 0;
+      }
+    }
+  }
+  const int any = __syncthreads_or(found);
+  if (threadIdx.x == 0) keep[win] = any ? 1 : 0;
+}
+
+// window_blend_kernel for a compact prediction buffer and a body mask: a voxel with mask 0 is
+// stored as +0 without reading a prediction; any other voxel accumulates its covering windows
+// exactly as window_blend_kernel does (same order, same separate multiply / add / divide), reading
+// window `win` from row slot[win] of preds, and the quotient is multiplied by the mask value.
+// A covering window without a row (slot < 0: the caller broke the contract) is left out.
+template <typename M>
+__global__ __launch_bounds__(256) void window_blend_masked_kernel(
+    const float* __restrict__ preds, const int* __restrict__ slot, const int* __restrict__ zp, int nz,
+    const int* __restrict__ yp, int ny, const int* __restrict__ xp, int nx,
+    const float* __restrict__ imp, const M* __restrict__ mask, int D, int H, int W, int pd, int ph,
+    int pw, float* __restrict__ prob) {
+  const long long V = (long long)D * H * W, P = (long long)pd * ph * pw;
+  for (long long v = blockIdx.x * 256ll + threadIdx.x; v < V; v += (long long)gridDim.x * 256) {
+    const float m = (float)mask[v];
+    if (m == 0.f) {
+      prob[v] = 0.f;
+      continue;
+    }
+    const int x = (int)(v % W), t = (int)(v / W), y = t % H, z = t / H;
+    int z_lo, z_hi, y_lo, y_hi, x_lo, x_hi;
+    cover(zp, nz, pd, z, z_lo, z_hi);
+    cover(yp, ny, ph, y, y_lo, y_hi);
+    cover(xp, nx, pw, x, x_lo, x_hi);
+    float acc = 0.f, cnt = 0.f;
+    for (int iz = z_lo; iz < z_hi; ++iz)
+      for (int iy = y_lo; iy < y_hi; ++iy)
+        for (int ix = x_lo; ix < x_hi; ++ix) {
+          const long long li = ((long long)(z - zp[iz]) * ph + (y - yp[iy])) * pw + (x - xp[ix]);
+          const int s = slot[((long long)iz * ny + iy) * nx + ix];
+          if (s < 0) continue;
+          const float wgt = imp[li];
+          acc = __fadd_rn(acc, __fmul_rn(preds[s * P + li], wgt));
+          cnt = __fadd_rn(cnt, wgt);
+        }
+    prob[v] = __fmul_rn(cnt > 0.f ? __fdiv_rn(acc, cnt) : acc, m);
+  }
+}
+
 }  // namespace
 
 extern "C" {
@@ -89,6 +188,45 @@ int l3u_window_blend(const float* preds, const int* zpos, int nz, const int* ypo
   if (nb > 65536) nb = 65536;
   hipLaunchKernelGGL(window_blend_kernel, dim3((int)nb), dim3(256), 0, stream, preds, zpos, nz, ypos,
                      ny, xpos, nx, imp, D, H, W, pd, ph, pw, prob);
+  L3U_CHECK_LAUNCH();
+}
+
+int l3u_window_occupancy(const void* mask, int mask_dtype, int D, int H, int W, const int* zpos,
+                         int nz, const int* ypos, int ny, const int* xpos, int nx, int pd, int ph,
+                         int pw, int* keep, hipStream_t stream) {
+  L3U_REQUIRE(D > 0 && H > 0 && W > 0 && nz > 0 && ny > 0 && nx > 0 && pd > 0 && ph > 0 && pw > 0);
+  L3U_REQUIRE(mask_dtype == 0 || mask_dtype == 2);
+  const long long nwin = (long long)nz * ny * nx;
+  L3U_REQUIRE(nwin <= 0x7fffffffll);
+  const dim3 grid((int)nwin), block(kOccThreads);
+  if (mask_dtype == 0)
+    hipLaunchKernelGGL(window_occupancy_kernel<float>, grid, block, 0, stream,
+                       static_cast<const float*>(mask), D, H, W, zpos, ypos, ny, xpos, nx, pd, ph,
+                       pw, keep);
+  else
+    hipLaunchKernelGGL(window_occupancy_kernel<unsigned char>, grid, block, 0, stream,
+                       static_cast<const unsigned char*>(mask), D, H, W, zpos, ypos, ny, xpos, nx,
+                       pd, ph, pw, keep);
+  L3U_CHECK_LAUNCH();
+}
+
+int l3u_window_blend_masked(const float* preds, const int* slot, const int* zpos, int nz,
+                            const int* ypos, int ny, const int* xpos, int nx, const float* imp,
+                            const void* mask, int mask_dtype, int D, int H, int W, int pd, int ph,
+                            int pw, float* prob, hipStream_t stream) {
+  L3U_REQUIRE(D > 0 && H > 0 && W > 0 && nz > 0 && ny > 0 && nx > 0 && pd > 0 && ph > 0 && pw > 0);
+  L3U_REQUIRE(mask_dtype == 0 || mask_dtype == 2);
+  const long long V = (long long)D * H * W;
+  long long nb = (V + 255) / 256;
+  if (nb > 65536) nb = 65536;
+  if (mask_dtype == 0)
+    hipLaunchKernelGGL(window_blend_masked_kernel<float>, dim3((int)nb), dim3(256), 0, stream, preds,
+                       slot, zpos, nz, ypos, ny, xpos, nx, imp, static_cast<const float*>(mask), D,
+                       H, W, pd, ph, pw, prob);
+  else
+    hipLaunchKernelGGL(window_blend_masked_kernel<unsigned char>, dim3((int)nb), dim3(256), 0,
+                       stream, preds, slot, zpos, nz, ypos, ny, xpos, nx, imp,
+                       static_cast<const unsigned char*>(mask), D, H, W, pd, ph, pw, prob);
   L3U_CHECK_LAUNCH();
 }
 

@@ -52,6 +52,7 @@ def load():
     importlib.import_module(ALIAS + ".lesion")
     importlib.import_module(ALIAS + ".patches")
     importlib.import_module(ALIAS + ".preprocess")
+    importlib.import_module(ALIAS + ".inference")
     return mod
 
 

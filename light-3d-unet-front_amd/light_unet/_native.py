@@ -67,6 +67,10 @@ _SIGS = {
     "l3u_ftl_reduce": [P, I, P, P],
     "l3u_window_gather": [P, I, I, I, P, I, I, I, I, P, P],
     "l3u_window_blend": [P, P, I, P, I, P, I, P, I, I, I, I, I, I, P, P],
+    # windows outside the body mask: (mask, mask_dtype, D, H, W, grid, patch, keep) and the blend
+    # over compact predictions (preds, slot, grid, imp, mask, mask_dtype, D, H, W, patch, prob)
+    "l3u_window_occupancy": [P, I, I, I, I, P, I, P, I, P, I, I, I, I, P, P],
+    "l3u_window_blend_masked": [P, P, P, I, P, I, P, I, P, P, I, I, I, I, I, I, I, P, P],
     "l3u_ftl_loss": [P, D, D, D, D, P, P],
     "l3u_ftl_bwd": [P, P, L, P, D, D, D, D, P, I, P, P],
     "l3u_reduce_segments": [P, P, I, P, P],

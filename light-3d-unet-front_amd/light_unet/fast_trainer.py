@@ -37,7 +37,9 @@ return value, but the probability maps stay on the device from the sliding windo
 `threshold_sensitivity_range` are evaluated by one `lesion.sweep_metrics` call: one level
 encoding and one level-batched labelling per case instead of an upload and two labellings per
 case and threshold.  The captured network forward and the targets' labellings are kept per
-Trainer, so later epochs neither capture nor label the targets again.
+Trainer, so later epochs neither capture nor label the targets again.  A body mask whose product
+with the map numpy keeps in float32 goes into the sliding window (`body_mask=`): windows outside
+it are not run and the map arrives already multiplied by it.
 """
 import torch
 
@@ -328,11 +330,18 @@ def validate(self, epoch):
             for b in range(images.shape[0]):
                 pick = (lambda t: t[b, 0]) if images.ndim == 5 else (lambda t: t[b])
                 image = pick(images).to(device=dev, dtype=torch.float32)
+                mask = pick(body_masks) if (apply_body_mask and body_masks is not None) else None
+                # a mask whose product with the map numpy keeps in float32 goes into the sliding
+                # window: windows outside it are not run and the map comes back multiplied by it
+                # (the float32 product the metrics would form), so the metrics get no mask
+                kw = {}
+                if mask is not None and lesion._np_kind(mask) == "f32" \
+                        and tuple(mask.shape) == tuple(image.shape):
+                    kw["body_mask"], mask = mask, None
                 prob = sliding_window_inference_3d(image=image, model=self.model,
                                                    patch_size=patch_size, overlap=0.5, device=dev,
                                                    use_gaussian=True, output="device",
-                                                   forward_cache=state["forward"])
-                mask = pick(body_masks) if (apply_body_mask and body_masks is not None) else None
+                                                   forward_cache=state["forward"], **kw)
                 # numpy's prob_map * body_mask with the mask's own dtype (a host tensor becomes the
                 # numpy array the reference multiplies by)
                 masks.append(mask.cpu().numpy() if isinstance(mask, torch.Tensor) and not mask.is_cuda

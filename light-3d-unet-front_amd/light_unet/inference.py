@@ -1,0 +1,39 @@
+"""The compute of the reference Inferencer.infer_case (inferencer.py:147-167) without its files:
+sliding window -> body mask -> bounding boxes, on the device from the image to the boxes.
+
+The reference runs every window, downloads the map, multiplies it by the body mask on the host
+and uploads nothing again only because its connected components run on the host too.  Here the
+mask goes into the sliding window (windows outside it are not run, utils.py `body_mask`), the
+masked map stays on the device for lesion.extract_bboxes and is downloaded once, for the caller
+to save.  Reading the NIfTI image / mask and writing the map and the JSON stay with the caller.
+"""
+from . import lesion
+from .utils import sliding_window_inference_3d
+
+
+def infer_volume(image, model, config, body_mask=None, spacing=(4.0, 4.0, 4.0), threshold=None,
+                 forward_cache=None):
+    """(prob_map, bboxes) of one case: prob_map the float32 numpy [D, H, W] map the reference
+    saves (times `body_mask` when config["data"]["body_mask"] has both `enabled` and
+    `apply_to_inference`, inferencer.py:136-137, :161-162; otherwise the mask is ignored), bboxes
+    what Inferencer.extract_bboxes returns for it at `threshold` (default
+    config["validation"]["default_threshold"]) with data.volume_threshold.inference_cc and
+    data.bbox_expansion_voxels.  `image` and `body_mask` may be numpy arrays or device tensors
+    (preprocess_volume(output="device") feeds this with no host pass); `forward_cache` as in
+    sliding_window_inference_3d.  The mask's dtype is one the sliding window takes (the reference
+    loads it as bool); any other raises its ValueError."""
+    data = config["data"]
+    bm = config.get("data", {}).get("body_mask", {})
+    apply_mask = bm.get("apply_to_inference", False) and bm.get("enabled", False)
+    mask = body_mask if apply_mask else None
+    if threshold is None:
+        threshold = config["validation"]["default_threshold"]
+    device = next(model.parameters()).device
+    prob = sliding_window_inference_3d(image=image, model=model,
+                                       patch_size=tuple(data["patch_size"]), overlap=0.5,
+                                       device=device, use_gaussian=True, output="device",
+                                       forward_cache=forward_cache, body_mask=mask)
+    bboxes = lesion.extract_bboxes(prob, threshold=threshold,
+                                   min_volume_cc=data["volume_threshold"]["inference_cc"],
+                                   spacing=spacing, expansion_voxels=data["bbox_expansion_voxels"])
+    return prob.cpu().numpy(), bboxes   # the one download

@@ -136,11 +136,47 @@ def _forward_for(model, vol, d, h, w, patch, B, device, forward_cache):
     return fwd.bind(vol, d, h, w)
 
 
+_MASK_DTYPES = "bool, uint8, int8, int16, float32"
+
+
+def _checked_body_mask(body_mask, shape):
+    """`body_mask` (numpy array or tensor) as a [D, H, W] float32 or uint8 array / tensor whose
+    float32 value per voxel is what numpy's `prob_map * body_mask` multiplies by: bool is viewed
+    as uint8, int8 / int16 are converted to float32 (exact).  ValueError for any other dtype
+    (numpy would promote the product to float64) and for a shape other than `shape`.  No device
+    call is made here."""
+    m = body_mask
+    is_t = isinstance(m, torch.Tensor)
+    if not is_t:
+        m = np.asarray(m)
+    if len(m.shape) == 4 and m.shape[0] == 1:
+        m = m[0]
+    if tuple(m.shape) != tuple(shape):
+        raise ValueError(f"body_mask has shape {tuple(m.shape)}, the image {tuple(shape)}")
+    if is_t:
+        if m.dtype == torch.bool:
+            return m.contiguous().view(torch.uint8)
+        if m.dtype in (torch.int8, torch.int16):
+            return m.to(torch.float32)
+        if m.dtype in (torch.uint8, torch.float32):
+            return m
+    else:
+        if m.dtype == np.bool_:
+            return np.ascontiguousarray(m).view(np.uint8)
+        if m.dtype in (np.dtype(np.int8), np.dtype(np.int16)):
+            return m.astype(np.float32)
+        if m.dtype in (np.dtype(np.uint8), np.dtype(np.float32)):
+            return m
+    raise ValueError(f"body_mask dtype {m.dtype} is not one of {_MASK_DTYPES} (numpy would "
+                     "promote prob_map * body_mask to float64: multiply such a mask on the host)")
+
+
 def sliding_window_inference_3d(image: np.ndarray, model: torch.nn.Module,
                                 patch_size: Tuple[int, int, int] = (48, 48, 48),
                                 overlap: float = 0.5, device: torch.device = None,
                                 use_gaussian: bool = True, window_batch: int = 16,
-                                group=None, output: str = "numpy", forward_cache=None):
+                                group=None, output: str = "numpy", forward_cache=None,
+                                body_mask=None, stats=None):
     """utils.py:11-139.  `window_batch` windows run per forward (extra keyword; the result
     does not depend on it).
 
@@ -156,7 +192,22 @@ def sliding_window_inference_3d(image: np.ndarray, model: torch.nn.Module,
     host.  `forward_cache` (a dict the caller keeps, e.g. across the cases and epochs of a
     validation) stores the captured network forward, so later calls with the same model, window
     batch, patch and activation dtype replay it instead of capturing again; the result is bitwise
-    the uncached one."""
+    the uncached one.
+
+    `body_mask` (extra keyword; a numpy array or a tensor of the image's shape, dtype bool, uint8,
+    int8, int16 or float32): the result is the map times float32(body_mask), what the reference's
+    callers compute right after this call (trainer.py:401-402, inferencer.py:161-162), bit for bit
+    at world size 1 -- but windows without a nonzero mask voxel are not run.  l3u_window_occupancy
+    marks the windows to keep, the flags are read back once, only the kept windows (in grid order,
+    padded to whole batches of the same `window_batch`, so the captured forwards are the ones of a
+    call without a mask) are gathered and run, and l3u_window_blend_masked blends them through a
+    slot table, storing 0 where the mask is 0.  A skipped window only covers voxels the mask
+    zeroes, and a voxel the mask keeps has all its windows kept, so every stored sum has the same
+    terms in the same order.  With an all-zero mask no forward runs and nothing is captured.  With
+    `group`, the ranks split the kept batches; voxels outside the mask are exactly 0.
+
+    `stats` (extra keyword; a dict) is filled with `windows` (the grid), `kept` (windows run by
+    all ranks together) and `forwards` (window batches this rank ran)."""
     if output not in ("numpy", "device"):
         raise ValueError(f"output must be 'numpy' or 'device', got {output!r}")
     if device is None:
@@ -166,6 +217,8 @@ def sliding_window_inference_3d(image: np.ndarray, model: torch.nn.Module,
         image = image[0]
     if len(image.shape) != 3:
         raise ValueError(f"Expected 3D image [D, H, W], got shape {image.shape}")
+    if body_mask is not None:
+        body_mask = _checked_body_mask(body_mask, image.shape)
     nat.require_device(torch.empty(0, device=device))
     d, h, w = image.shape
     pd, ph, pw = patch_size
@@ -187,15 +240,45 @@ def sliding_window_inference_3d(image: np.ndarray, model: torch.nn.Module,
                 vol = image.to(device=device, dtype=torch.float32).contiguous()
             else:
                 vol = torch.from_numpy(np.ascontiguousarray(image, dtype=np.float32)).to(device)
-            pos_all = torch.tensor(order + [order[-1]] * ((-nwin) % B), dtype=torch.int32,
-                                   device=device)
+            zt, yt, xt = (torch.tensor(v, dtype=torch.int32, device=device) for v in (zs, ys, xs))
             world, rank = 1, 0
             if group is not None:
                 import torch.distributed as dist
                 world, rank = dist.get_world_size(group), dist.get_rank(group)
+            nrun, slot, mask, mcode = nwin, None, None, 0   # nrun windows run, in grid order
+            if body_mask is not None:
+                if isinstance(body_mask, torch.Tensor):
+                    mask = body_mask.to(device).contiguous()
+                else:
+                    mask = torch.from_numpy(np.ascontiguousarray(body_mask)).to(device)
+                mcode = 0 if mask.dtype == torch.float32 else 2   # l3u_pp_pack's dtype codes
+                keep = torch.empty(nwin, dtype=torch.int32, device=device)
+                nat.call("l3u_window_occupancy", mask.data_ptr(), mcode, d, h, w, zt.data_ptr(),
+                         len(zs), yt.data_ptr(), len(ys), xt.data_ptr(), len(xs), pd, ph, pw,
+                         keep.data_ptr(), nat.stream())
+                kept = np.flatnonzero(keep.cpu().numpy())   # the one read-back
+                nrun = len(kept)
+            if stats is not None:
+                stats.update(windows=nwin, kept=nrun,
+                             forwards=len(range(rank, -(-nrun // B), world)))
+            if nrun == 0:   # nothing inside the mask: no forward, no capture
+                prob = torch.zeros(d, h, w, device=device)
+                return prob if output == "device" else prob.cpu().numpy()
+            if mask is None:
+                pos_all = torch.tensor(order + [order[-1]] * ((-nwin) % B), dtype=torch.int32,
+                                       device=device)
+            else:
+                # the kept windows' positions, padded to whole batches with the last one, and
+                # the slot table (window -> row of preds, -1: not run) in one upload
+                rows = np.concatenate([kept, np.repeat(kept[-1:], (-nrun) % B)])
+                slot_h = np.full(nwin, -1, dtype=np.int32)
+                slot_h[kept] = np.arange(nrun, dtype=np.int32)
+                table = np.concatenate([np.asarray(order, dtype=np.int32)[rows].ravel(), slot_h])
+                table = torch.from_numpy(table).to(device)
+                pos_all, slot = table[:3 * len(rows)].view(-1, 3), table[3 * len(rows):]
             preds = (torch.zeros if world > 1 else torch.empty)(pos_all.shape[0], P, device=device)
             fwd = _forward_for(model, vol, d, h, w, (pd, ph, pw), B, device, forward_cache)
-            for bi, b0 in enumerate(range(0, nwin, B)):
+            for bi, b0 in enumerate(range(0, nrun, B)):
                 if bi % world != rank:   # another rank's batch
                     continue
                 fwd.pos.copy_(pos_all[b0:b0 + B])
@@ -203,12 +286,17 @@ def sliding_window_inference_3d(image: np.ndarray, model: torch.nn.Module,
                 if out.dim() != 5 or tuple(out.shape[2:]) != (pd, ph, pw):
                     raise ValueError(f"Expected 3D model output, got shape {tuple(out.shape)}")
                 preds[b0:b0 + B].copy_(out.reshape(B, P))
-            zt, yt, xt = (torch.tensor(v, dtype=torch.int32, device=device) for v in (zs, ys, xs))
             impt = torch.from_numpy(imp).to(device)
             prob = torch.empty(d, h, w, device=device)
-            nat.call("l3u_window_blend", preds.data_ptr(), zt.data_ptr(), len(zs), yt.data_ptr(),
-                     len(ys), xt.data_ptr(), len(xs), impt.data_ptr(), d, h, w, pd, ph, pw,
-                     prob.data_ptr(), nat.stream())
+            if mask is None:
+                nat.call("l3u_window_blend", preds.data_ptr(), zt.data_ptr(), len(zs),
+                         yt.data_ptr(), len(ys), xt.data_ptr(), len(xs), impt.data_ptr(), d, h, w,
+                         pd, ph, pw, prob.data_ptr(), nat.stream())
+            else:   # each rank's share times the mask: exact zeros outside it after the sum too
+                nat.call("l3u_window_blend_masked", preds.data_ptr(), slot.data_ptr(),
+                         zt.data_ptr(), len(zs), yt.data_ptr(), len(ys), xt.data_ptr(), len(xs),
+                         impt.data_ptr(), mask.data_ptr(), mcode, d, h, w, pd, ph, pw,
+                         prob.data_ptr(), nat.stream())
             if world > 1:
                 dist.all_reduce(prob, op=dist.ReduceOp.SUM, group=group)
             return prob if output == "device" else prob.cpu().numpy()
