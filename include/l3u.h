@@ -42,7 +42,7 @@ typedef unsigned short l3u_bf16;   /* bfloat16 bit pattern (torch.bfloat16 stora
  * another.  3: l3u_norm_src.rank1, L3U_ADAMW_TICKET_INTS tickets, the l3u_sblock_* entry points
  * removed (round 3); the round-4 entry points.  5: l3u_pw_bwd_chunk (round 6).  Added since
  * without a new version (additive, nothing existing changed): l3u_window_occupancy,
- * l3u_window_blend_masked. */
+ * l3u_window_blend_masked, l3u_window_gather_flip, l3u_window_tta_merge. */
 #define L3U_ABI_VERSION 5
 int l3u_abi_version(void);
 
@@ -744,6 +744,26 @@ int l3u_window_blend_masked(const float* preds, const int* slot, const int* zpos
                             const int* ypos, int ny, const int* xpos, int nx, const float* imp,
                             const void* mask, int mask_dtype, int D, int H, int W, int pd, int ph,
                             int pw, float* prob, hipStream_t stream);
+
+/* Mirror test-time augmentation of the sliding window (not in the reference).  A flip code 0..7
+ * has bit a set when axis a (0: D, 1: H, 2: W) of the zero-padded pd x ph x pw window is reversed
+ * (F_c; the padding moves to the low end of a reversed axis; F_c is its own inverse).  `code` and
+ * `codes` are HOST arrays: they are checked before anything is launched (a value outside 0..7
+ * returns hipErrorInvalidValue) and travel in the launch arguments, so a captured launch keeps
+ * the codes it was captured with.
+ * gather_flip: out[r] = F_code[r] of the window l3u_window_gather cuts at pos[r] (pos: device,
+ *              R x {z, y, x}); with every code 0 bit for bit l3u_window_gather's output.
+ * tta_merge:   rows: [G*K][pd*ph*pw], the K predictions of window g adjacent (term j computed on
+ *              the F_codes[j] input).  dst[g][i] = (rows[g*K][F_codes[0](i)] + rows[g*K + 1][..] +
+ *              ...) * (1 / K): separate fp32 adds in term order starting from term 0, then one
+ *              multiply; K in {1, 2, 4, 8} (K = 1, code 0: a copy), G <= 65535.  One thread per
+ *              output element, no atomics; dst must not overlap rows.
+ * Both take 16-byte loads and stores when pw % 4 == 0 and the row pointers are 16-byte aligned
+ * (the gather: out; the merge: rows and dst), and an element-wise path otherwise.              */
+int l3u_window_gather_flip(const float* img, int D, int H, int W, const int* pos, const int* code,
+                           int R, int pd, int ph, int pw, float* out, hipStream_t stream);
+int l3u_window_tta_merge(const float* rows, const int* codes, int K, int G, int pd, int ph, int pw,
+                         float* dst, hipStream_t stream);
 
 /* storage casts (the bf16 network's input / input gradient); n elements                      */
 int l3u_cast_f32_bf16(const float* x, l3u_bf16* y, long long n, hipStream_t stream);

@@ -12,6 +12,9 @@
 //                  inferencer.py:161-162) without the forwards of windows the mask empties: which
 //                  windows hold a nonzero mask voxel, and the blend over a compact prediction
 //                  buffer that stores +0 wherever the mask is 0
+//   window_gather_flip / window_tta_merge  mirror test-time augmentation (not in the reference):
+//                  the gather with a flip code per row, and the mean of a window's K predictions,
+//                  each flipped back, written to the window's row of the prediction buffer
 #include "common.h"
 using namespace l3u;
 
@@ -164,6 +167,119 @@ __global__ __launch_bounds__(256) void window_blend_masked_kernel(
   }
 }
 
+// ---- mirror test-time augmentation ---------------------------------------------------------------
+// A flip code has bit a set when axis a (0: D, 1: H, 2: W) of the zero-padded window is reversed.
+// The exports read the codes from HOST arrays, check them there and hand them to the kernels in
+// the launch arguments: the gather 4 bits per row (a launch covers at most kFlipRows rows), the
+// merge 3 bits per term.
+constexpr int kFlipRows = 1024;
+struct FlipCodes { unsigned w[kFlipRows / 8]; };
+L3U_DEV int flip_code(const FlipCodes& c, int r) { return (int)((c.w[r >> 3] >> ((r & 7) * 4)) & 7u); }
+L3U_DEV f4_t rev4(f4_t v) { return f4_t{v[3], v[2], v[1], v[0]}; }
+
+// window_gather_kernel with a flip per row: out[b][l][j][k] is the padded window's element at the
+// mirrored index along every axis the row's code reverses (so the padding moves to the low end).
+// VEC (pw % 4 == 0, out 16-byte aligned): a thread owns the 4 consecutive output elements of one
+// W-row; their sources are 4 consecutive volume elements (read in descending order under a W flip),
+// taken as one 16-byte load when they lie inside the volume on a 16-byte boundary, else one by one.
+// Consecutive lanes read consecutive addresses with or without the W flip (descending lane order
+// under it), so a wave's loads cover the same cache lines either way.
+template <bool VEC>
+__global__ __launch_bounds__(256) void window_gather_flip_kernel(
+    const float* __restrict__ img, int D, int H, int W, const int* __restrict__ pos, FlipCodes codes,
+    int pd, int ph, int pw, float* __restrict__ out) {
+  constexpr int E = VEC ? 4 : 1;
+  const int b = blockIdx.y;
+  const int c = flip_code(codes, b);
+  const bool fz = (c & 1) != 0, fy = (c & 2) != 0, fx = (c & 4) != 0;
+  const long long P = (long long)pd * ph * pw, n = P / E;
+  const int z0 = pos[3 * b], y0 = pos[3 * b + 1], x0 = pos[3 * b + 2];
+  float* o = out + (long long)b * P;
+  for (long long i = blockIdx.x * 256ll + threadIdx.x; i < n; i += (long long)gridDim.x * 256) {
+    const long long e = i * E;
+    const int k = (int)(e % pw), t = (int)(e / pw), j = t % ph, l = t / ph;
+    const int z = z0 + (fz ? pd - 1 - l : l), y = y0 + (fy ? ph - 1 - j : j);
+    const bool row_in = z < D && y < H;
+    const long long ro = ((long long)z * H + y) * W;   // used only when row_in
+    if constexpr (VEC) {
+      const int xs = x0 + (fx ? pw - 4 - k : k);   // the quad's lowest source x
+      f4_t v = {0.f, 0.f, 0.f, 0.f};
+      if (row_in) {
+        const float* s = img + ro + xs;
+        if (xs + 3 < W && ((uintptr_t)s & 15) == 0) {
+          v = ldv4(s);
+        } else {
+#pragma unroll
+          for (int q = 0; q < 4; ++q)
+            if (xs + q < W) v[q] = s[q];
+        }
+      }
+      *reinterpret_cast<f4_t*>(o + e) = fx ? rev4(v) : v;
+    } else {
+      const int x = x0 + (fx ? pw - 1 - k : k);
+      o[e] = (row_in && x < W) ? img[ro + x] : 0.f;
+    }
+  }
+}
+
+// dst[g][i] = (rows[g*K][F_c0(i)] + rows[g*K + 1][F_c1(i)] + ...) * (1 / K): the K predictions of
+// a window, each flipped back, summed in term order with separate fp32 adds starting from term 0,
+// then one multiply (exact: K is a power of two).  One thread per output element (VEC: per 4
+// consecutive ones of a W-row; the mirrored quad of a W-flipped term is one aligned 16-byte load,
+// reversed in registers), all K loads requested before the first add, no atomics.
+template <int K, bool VEC>
+__global__ __launch_bounds__(256) void window_tta_merge_kernel(
+    const float* __restrict__ rows, unsigned codes, int pd, int ph, int pw, float* __restrict__ dst) {
+  constexpr int E = VEC ? 4 : 1;
+  constexpr float inv = 1.f / K;
+  const long long P = (long long)pd * ph * pw, n = P / E;
+  const float* src = rows + (long long)blockIdx.y * K * P;
+  float* o = dst + (long long)blockIdx.y * P;
+  for (long long i = blockIdx.x * 256ll + threadIdx.x; i < n; i += (long long)gridDim.x * 256) {
+    const long long e = i * E;
+    const int k = (int)(e % pw), t = (int)(e / pw), j = t % ph, l = t / ph;
+    if constexpr (VEC) {
+      f4_t v[K];
+#pragma unroll
+      for (int q = 0; q < K; ++q) {
+        const unsigned c = codes >> (3 * q);
+        const int ls = (c & 1u) ? pd - 1 - l : l, js = (c & 2u) ? ph - 1 - j : j;
+        const int ks = (c & 4u) ? pw - 4 - k : k;
+        const f4_t a = ldv4(src + q * P + ((long long)ls * ph + js) * pw + ks);
+        v[q] = (c & 4u) ? rev4(a) : a;
+      }
+      f4_t s = v[0];
+#pragma unroll
+      for (int q = 1; q < K; ++q) s = s + v[q];
+      *reinterpret_cast<f4_t*>(o + e) = s * inv;
+    } else {
+      float v[K];
+#pragma unroll
+      for (int q = 0; q < K; ++q) {
+        const unsigned c = codes >> (3 * q);
+        const int ls = (c & 1u) ? pd - 1 - l : l, js = (c & 2u) ? ph - 1 - j : j;
+        const int ks = (c & 4u) ? pw - 1 - k : k;
+        v[q] = src[q * P + ((long long)ls * ph + js) * pw + ks];
+      }
+      float s = v[0];
+#pragma unroll
+      for (int q = 1; q < K; ++q) s = __fadd_rn(s, v[q]);
+      o[e] = __fmul_rn(s, inv);
+    }
+  }
+}
+
+template <int K>
+void tta_merge_launch(bool vec, dim3 grid, hipStream_t stream, const float* rows, unsigned codes,
+                      int pd, int ph, int pw, float* dst) {
+  if (vec)
+    hipLaunchKernelGGL((window_tta_merge_kernel<K, true>), grid, dim3(256), 0, stream, rows, codes,
+                       pd, ph, pw, dst);
+  else
+    hipLaunchKernelGGL((window_tta_merge_kernel<K, false>), grid, dim3(256), 0, stream, rows, codes,
+                       pd, ph, pw, dst);
+}
+
 }  // namespace
 
 extern "C" {
@@ -227,6 +343,56 @@ int l3u_window_blend_masked(const float* preds, const int* slot, const int* zpos
     hipLaunchKernelGGL(window_blend_masked_kernel<unsigned char>, dim3((int)nb), dim3(256), 0,
                        stream, preds, slot, zpos, nz, ypos, ny, xpos, nx, imp,
                        static_cast<const unsigned char*>(mask), D, H, W, pd, ph, pw, prob);
+  L3U_CHECK_LAUNCH();
+}
+
+int l3u_window_gather_flip(const float* img, int D, int H, int W, const int* pos, const int* code,
+                           int R, int pd, int ph, int pw, float* out, hipStream_t stream) {
+  L3U_REQUIRE(D > 0 && H > 0 && W > 0 && R > 0 && pd > 0 && ph > 0 && pw > 0 && code != nullptr);
+  for (int r = 0; r < R; ++r) L3U_REQUIRE(code[r] >= 0 && code[r] <= 7);
+  const long long P = (long long)pd * ph * pw;
+  const bool vec = pw % 4 == 0 && ((uintptr_t)out & 15) == 0;   // then every row and quad of out is aligned
+  const long long n = vec ? P / 4 : P;
+  long long nb = vec ? (n + 255) / 256 : (n + 1023) / 1024;
+  if (nb > 1024) nb = 1024;
+  for (int r0 = 0; r0 < R; r0 += kFlipRows) {
+    const int nr = R - r0 < kFlipRows ? R - r0 : kFlipRows;
+    FlipCodes fc = {};
+    for (int r = 0; r < nr; ++r) fc.w[r >> 3] |= (unsigned)code[r0 + r] << ((r & 7) * 4);
+    const dim3 grid((int)nb, nr);
+    if (vec)
+      hipLaunchKernelGGL(window_gather_flip_kernel<true>, grid, dim3(256), 0, stream, img, D, H, W,
+                         pos + 3ll * r0, fc, pd, ph, pw, out + r0 * P);
+    else
+      hipLaunchKernelGGL(window_gather_flip_kernel<false>, grid, dim3(256), 0, stream, img, D, H, W,
+                         pos + 3ll * r0, fc, pd, ph, pw, out + r0 * P);
+    const hipError_t err = hipGetLastError();
+    if (err != hipSuccess) return (int)err;
+  }
+  return (int)hipSuccess;
+}
+
+int l3u_window_tta_merge(const float* rows, const int* codes, int K, int G, int pd, int ph, int pw,
+                         float* dst, hipStream_t stream) {
+  L3U_REQUIRE((K == 1 || K == 2 || K == 4 || K == 8) && G > 0 && pd > 0 && ph > 0 && pw > 0);
+  L3U_REQUIRE(G <= 65535 && codes != nullptr);
+  unsigned packed = 0;
+  for (int q = 0; q < K; ++q) {
+    L3U_REQUIRE(codes[q] >= 0 && codes[q] <= 7);
+    packed |= (unsigned)codes[q] << (3 * q);
+  }
+  const long long P = (long long)pd * ph * pw;
+  const bool vec = pw % 4 == 0 && (((uintptr_t)rows | (uintptr_t)dst) & 15) == 0;
+  const long long n = vec ? P / 4 : P;
+  long long nb = (n + 255) / 256;
+  if (nb > 4096) nb = 4096;
+  const dim3 grid((int)nb, G);
+  switch (K) {
+    case 1: tta_merge_launch<1>(vec, grid, stream, rows, packed, pd, ph, pw, dst); break;
+    case 2: tta_merge_launch<2>(vec, grid, stream, rows, packed, pd, ph, pw, dst); break;
+    case 4: tta_merge_launch<4>(vec, grid, stream, rows, packed, pd, ph, pw, dst); break;
+    default: tta_merge_launch<8>(vec, grid, stream, rows, packed, pd, ph, pw, dst); break;
+  }
   L3U_CHECK_LAUNCH();
 }
 

@@ -178,7 +178,10 @@ def install(fast_step=False, lesion=True, device_patches=False, fast_validate=Fa
     the metrics, the captured network forward is reused across cases and epochs, and every
     threshold of threshold_sensitivity_range is evaluated from one level-batched labelling per
     case (lesion.sweep_metrics).  Same return value; the original stays reachable as
-    Trainer._l3u_reference_validate.  Needs light_unet.core.trainer.
+    Trainer._l3u_reference_validate.  Needs light_unet.core.trainer.  It also reads one config key
+    the reference does not have, validation.tta_flips (default: absent, off): None, "all" or a
+    list of window axes out of 0, 1, 2 -- the sliding window's mirror test-time augmentation
+    (light_unet/utils.py `tta_flips`).
 
     device_locations=True also replaces PatchDataset._sample_locations (patch_dataset.py:74-100):
     every case's label and body mask are read as the reference reads them and uploaded (label as

@@ -71,6 +71,10 @@ _SIGS = {
     # over compact predictions (preds, slot, grid, imp, mask, mask_dtype, D, H, W, patch, prob)
     "l3u_window_occupancy": [P, I, I, I, I, P, I, P, I, P, I, I, I, I, P, P],
     "l3u_window_blend_masked": [P, P, P, I, P, I, P, I, P, P, I, I, I, I, I, I, I, P, P],
+    # mirror test-time augmentation: (img, D, H, W, pos, code[R] on the HOST, R, patch, out) and
+    # (rows, codes[K] on the HOST, K, G, patch, dst)
+    "l3u_window_gather_flip": [P, I, I, I, P, P, I, I, I, I, P, P],
+    "l3u_window_tta_merge": [P, P, I, I, I, I, I, P, P],
     "l3u_ftl_loss": [P, D, D, D, D, P, P],
     "l3u_ftl_bwd": [P, P, L, P, D, D, D, D, P, I, P, P],
     "l3u_reduce_segments": [P, P, I, P, P],

@@ -39,7 +39,9 @@ encoding and one level-batched labelling per case instead of an upload and two l
 case and threshold.  The captured network forward and the targets' labellings are kept per
 Trainer, so later epochs neither capture nor label the targets again.  A body mask whose product
 with the map numpy keeps in float32 goes into the sliding window (`body_mask=`): windows outside
-it are not run and the map arrives already multiplied by it.
+it are not run and the map arrives already multiplied by it.  One config key the reference does
+not have, `validation.tta_flips` (absent: off), turns on the sliding window's mirror test-time
+augmentation.
 """
 import torch
 
@@ -315,6 +317,8 @@ def validate(self, epoch):
     patch_size = tuple(self.config["data"]["patch_size"])
     bm = self.config.get("data", {}).get("body_mask", {})
     apply_body_mask = bm.get("apply_to_validation", False) and bm.get("enabled", False)
+    # mirror test-time augmentation: a key the reference configs do not have (absent: off)
+    tta_flips = self.config["validation"].get("tta_flips")
     dev = torch.device(self.device)
     with torch.no_grad():
         for batch in _tqdm(self.val_loader, desc=f"Epoch {epoch+1} [Val]"):
@@ -334,7 +338,7 @@ def validate(self, epoch):
                 # a mask whose product with the map numpy keeps in float32 goes into the sliding
                 # window: windows outside it are not run and the map comes back multiplied by it
                 # (the float32 product the metrics would form), so the metrics get no mask
-                kw = {}
+                kw = {} if tta_flips is None else {"tta_flips": tta_flips}
                 if mask is not None and lesion._np_kind(mask) == "f32" \
                         and tuple(mask.shape) == tuple(image.shape):
                     kw["body_mask"], mask = mask, None

@@ -12,7 +12,7 @@ from .utils import sliding_window_inference_3d
 
 
 def infer_volume(image, model, config, body_mask=None, spacing=(4.0, 4.0, 4.0), threshold=None,
-                 forward_cache=None):
+                 forward_cache=None, tta_flips=None):
     """(prob_map, bboxes) of one case: prob_map the float32 numpy [D, H, W] map the reference
     saves (times `body_mask` when config["data"]["body_mask"] has both `enabled` and
     `apply_to_inference`, inferencer.py:136-137, :161-162; otherwise the mask is ignored), bboxes
@@ -21,7 +21,8 @@ def infer_volume(image, model, config, body_mask=None, spacing=(4.0, 4.0, 4.0), 
     data.bbox_expansion_voxels.  `image` and `body_mask` may be numpy arrays or device tensors
     (preprocess_volume(output="device") feeds this with no host pass); `forward_cache` as in
     sliding_window_inference_3d.  The mask's dtype is one the sliding window takes (the reference
-    loads it as bool); any other raises its ValueError."""
+    loads it as bool); any other raises its ValueError.  `tta_flips` (default off) is the sliding
+    window's mirror test-time augmentation: None, "all" or the window axes to flip."""
     data = config["data"]
     bm = config.get("data", {}).get("body_mask", {})
     apply_mask = bm.get("apply_to_inference", False) and bm.get("enabled", False)
@@ -32,7 +33,8 @@ def infer_volume(image, model, config, body_mask=None, spacing=(4.0, 4.0, 4.0), 
     prob = sliding_window_inference_3d(image=image, model=model,
                                        patch_size=tuple(data["patch_size"]), overlap=0.5,
                                        device=device, use_gaussian=True, output="device",
-                                       forward_cache=forward_cache, body_mask=mask)
+                                       forward_cache=forward_cache, body_mask=mask,
+                                       tta_flips=tta_flips)
     bboxes = lesion.extract_bboxes(prob, threshold=threshold,
                                    min_volume_cc=data["volume_threshold"]["inference_cc"],
                                    spacing=spacing, expansion_voxels=data["bbox_expansion_voxels"])

@@ -11,7 +11,10 @@ reference, but instead of one bs=1 forward and two host round trips per window:
     same float32 operations (utils.py:125-135).
 A model that is not this package's Lightweight3DUNet is called eagerly per batch (same device
 gather / blend).  There is no CPU path: the volume is processed on `device`.
+Not in the reference: `tta_flips`, mirror test-time augmentation (l3u_window_gather_flip cuts the
+K flips of each window into one forward batch, l3u_window_tta_merge averages them back).
 """
+import ctypes
 from typing import Tuple
 
 import numpy as np
@@ -42,11 +45,24 @@ def window_positions(size: int, patch: int, stride: int):
     return pos or [0]
 
 
+def _gather_windows(vol, dims, pos, code, batch, patch, x):
+    """`batch` windows of `vol` at `pos` into `x`; with `code` (flip codes per row, a host int
+    array) each row flipped by its code."""
+    D, H, W = dims
+    if code is None:
+        nat.call("l3u_window_gather", vol.data_ptr(), D, H, W, pos.data_ptr(), batch, *patch,
+                 x.data_ptr(), nat.stream())
+    else:
+        nat.call("l3u_window_gather_flip", vol.data_ptr(), D, H, W, pos.data_ptr(), code, batch,
+                 *patch, x.data_ptr(), nat.stream())
+
+
 class _GraphForward:
     """Forward of a fixed batch of windows as one replayed graph: gather -> network."""
 
-    def __init__(self, model, vol, D, H, W, patch, batch, device):
+    def __init__(self, model, vol, D, H, W, patch, batch, device, code=None):
         self.model, self.vol, self.dims, self.patch, self.batch = model, vol, (D, H, W), patch, batch
+        self.code = code   # per-row flip codes (a host int array) or None: the plain gather
         self.pos = torch.zeros(batch, 3, dtype=torch.int32, device=device)
         self.x = torch.empty(batch, 1, *patch, device=device)
         self.engine = getattr(model, "engine", None)
@@ -63,9 +79,7 @@ class _GraphForward:
                 self.out = self._run(flat)
 
     def _gather(self):
-        D, H, W = self.dims
-        nat.call("l3u_window_gather", self.vol.data_ptr(), D, H, W, self.pos.data_ptr(), self.batch,
-                 *self.patch, self.x.data_ptr(), nat.stream())
+        _gather_windows(self.vol, self.dims, self.pos, self.code, self.batch, self.patch, self.x)
 
     def _run(self, flat):
         self._gather()
@@ -104,26 +118,26 @@ class _CachedForward:
         with torch.cuda.graph(self.graph):
             self.out, _ = self.engine.forward(self.flat, self.x, training=False, save=False)
         _CachedForward.captures += 1
-        self.vol = self.dims = None
+        self.vol = self.dims = self.code = None
 
-    def bind(self, vol, D, H, W):
-        self.vol, self.dims = vol, (D, H, W)
+    def bind(self, vol, D, H, W, code=None):
+        self.vol, self.dims, self.code = vol, (D, H, W), code
         return self
 
     def __call__(self):
-        D, H, W = self.dims
-        nat.call("l3u_window_gather", self.vol.data_ptr(), D, H, W, self.pos.data_ptr(), self.batch,
-                 *self.patch, self.x.data_ptr(), nat.stream())
+        _gather_windows(self.vol, self.dims, self.pos, self.code, self.batch, self.patch, self.x)
         self.graph.replay()
         return self.out
 
 
-def _forward_for(model, vol, d, h, w, patch, B, device, forward_cache):
+def _forward_for(model, vol, d, h, w, patch, B, device, forward_cache, code=None):
     """The window-batch forward: a fresh _GraphForward, or with `forward_cache` (a dict) the
-    cached network graph of (model identity, window batch, patch, activation dtype)."""
+    cached network graph of (model identity, window batch, patch, activation dtype).  `code`:
+    the rows' flip codes (test-time augmentation); the cached graph holds no gather, so a plain
+    and a flipped call of the same batch share it."""
     engine = getattr(model, "engine", None)
     if forward_cache is None or engine is None:
-        return _GraphForward(model, vol, d, h, w, patch, B, device)
+        return _GraphForward(model, vol, d, h, w, patch, B, device, code)
     # the engine's current activation storage, which is what _GraphForward would capture with
     key = (id(model), int(B), tuple(patch), str(engine.act_dtype))
     fwd = forward_cache.get(key)
@@ -133,7 +147,7 @@ def _forward_for(model, vol, d, h, w, patch, B, device, forward_cache):
             fwd.flat.data_ptr() != model.flat_parameters().data_ptr():
         fwd = _CachedForward(model, patch, B, device)
         forward_cache[key] = fwd
-    return fwd.bind(vol, d, h, w)
+    return fwd.bind(vol, d, h, w, code)
 
 
 _MASK_DTYPES = "bool, uint8, int8, int16, float32"
@@ -171,12 +185,38 @@ def _checked_body_mask(body_mask, shape):
                      "promote prob_map * body_mask to float64: multiply such a mask on the host)")
 
 
+def tta_codes(tta_flips):
+    """The flip codes of mirror test-time augmentation, ascending (code 0, the identity, first):
+    bit a of a code is set when window axis a (0: D, 1: H, 2: W) is reversed, and the codes are
+    all those whose set bits lie within `tta_flips`.  `tta_flips`: None or () for off ([0]),
+    "all" for (0, 1, 2), or a sequence of distinct axes out of {0, 1, 2}.  ValueError for anything
+    else.  No device call is made here."""
+    if tta_flips is None:
+        return [0]
+    if isinstance(tta_flips, str):
+        if tta_flips != "all":
+            raise ValueError(f"tta_flips must be None, 'all' or a sequence of axes, got {tta_flips!r}")
+        tta_flips = (0, 1, 2)
+    try:
+        axes = list(tta_flips)
+    except TypeError:
+        raise ValueError(f"tta_flips must be None, 'all' or a sequence of axes, got {tta_flips!r}")
+    bits = 0
+    for a in axes:
+        if isinstance(a, bool) or not isinstance(a, (int, np.integer)) or not 0 <= a <= 2:
+            raise ValueError(f"tta_flips axes must be out of 0, 1, 2 (D, H, W), got {a!r}")
+        if bits >> int(a) & 1:
+            raise ValueError(f"tta_flips repeats axis {a}")
+        bits |= 1 << int(a)
+    return [c for c in range(8) if c & ~bits == 0]
+
+
 def sliding_window_inference_3d(image: np.ndarray, model: torch.nn.Module,
                                 patch_size: Tuple[int, int, int] = (48, 48, 48),
                                 overlap: float = 0.5, device: torch.device = None,
                                 use_gaussian: bool = True, window_batch: int = 16,
                                 group=None, output: str = "numpy", forward_cache=None,
-                                body_mask=None, stats=None):
+                                body_mask=None, stats=None, tta_flips=None):
     """utils.py:11-139.  `window_batch` windows run per forward (extra keyword; the result
     does not depend on it).
 
@@ -207,9 +247,31 @@ def sliding_window_inference_3d(image: np.ndarray, model: torch.nn.Module,
     `group`, the ranks split the kept batches; voxels outside the mask are exactly 0.
 
     `stats` (extra keyword; a dict) is filled with `windows` (the grid), `kept` (windows run by
-    all ranks together) and `forwards` (window batches this rank ran)."""
+    all ranks together) and `forwards` (window batches this rank ran).
+
+    `tta_flips` (extra keyword, not in the reference): mirror test-time augmentation.  None or ()
+    for off, "all" for (0, 1, 2), or a sequence of distinct axes out of {0, 1, 2}: D, H and W of
+    the window (anything else raises ValueError before any device call).  With k axes there are
+    K = 2**k flip codes (`tta_codes`): code c has bit a set when axis a is reversed, the codes are
+    all c whose set bits lie within the axes, ascending, the identity first.  For window w let x_w
+    be the zero-padded pd x ph x pw window as it is cut today and F_c the reversal of the listed
+    axes of that padded window (the padding moves to the low end; F_c is its own inverse).  The
+    window's prediction is
+        p_w = (F_c0(M(F_c0 x_w)) + F_c1(M(F_c1 x_w)) + ...) * float32(1 / K),
+    summed in float32 in ascending code order as separate adds starting from the code-0 term, then
+    one multiply (exact: K is a power of two).  The windows are then blended exactly as without
+    it -- same kernels, order and importance map; `body_mask` and `group` work as before.  This is
+    the map the plain call gives for a module whose forward is that expression.  A forward runs
+    R = K * max(1, B // K) rows (B the clipped `window_batch`), the K rows of a window adjacent
+    (l3u_window_gather_flip), and one l3u_window_tta_merge launch per forward writes the windows'
+    means into the prediction buffer, which keeps one row per window.  When K divides B the
+    forward has the plain call's batch and `forward_cache` replays the plain call's capture.
+    With test-time augmentation on, `stats` also gets `tta` (= K) and `forwards` counts the
+    R-row forwards; with it off the call is the one without the keyword, bit for bit."""
     if output not in ("numpy", "device"):
         raise ValueError(f"output must be 'numpy' or 'device', got {output!r}")
+    codes = tta_codes(tta_flips)
+    K = len(codes)
     if device is None:
         device = next(model.parameters()).device
     device = torch.device(device)
@@ -230,6 +292,9 @@ def sliding_window_inference_3d(image: np.ndarray, model: torch.nn.Module,
     order = [(z, y, x) for z in zs for y in ys for x in xs]   # the reference's loop order
     nwin = len(order)
     B = max(1, min(int(window_batch), nwin))
+    if K > 1:   # B windows per forward become B // K windows of K rows each
+        B = max(1, B // K)
+    R = K * B   # rows per forward
     P = pd * ph * pw
 
     was_training = model.training
@@ -261,6 +326,8 @@ def sliding_window_inference_3d(image: np.ndarray, model: torch.nn.Module,
             if stats is not None:
                 stats.update(windows=nwin, kept=nrun,
                              forwards=len(range(rank, -(-nrun // B), world)))
+                if K > 1:
+                    stats["tta"] = K
             if nrun == 0:   # nothing inside the mask: no forward, no capture
                 prob = torch.zeros(d, h, w, device=device)
                 return prob if output == "device" else prob.cpu().numpy()
@@ -277,15 +344,24 @@ def sliding_window_inference_3d(image: np.ndarray, model: torch.nn.Module,
                 table = torch.from_numpy(table).to(device)
                 pos_all, slot = table[:3 * len(rows)].view(-1, 3), table[3 * len(rows):]
             preds = (torch.zeros if world > 1 else torch.empty)(pos_all.shape[0], P, device=device)
-            fwd = _forward_for(model, vol, d, h, w, (pd, ph, pw), B, device, forward_cache)
+            row_code = merge_code = None
+            if K > 1:   # row g * K + j of a forward: window g under flip code j
+                row_code, merge_code = (ctypes.c_int * R)(*(codes * B)), (ctypes.c_int * K)(*codes)
+                pos_all = pos_all.repeat_interleave(K, dim=0)
+            fwd = _forward_for(model, vol, d, h, w, (pd, ph, pw), R, device, forward_cache, row_code)
             for bi, b0 in enumerate(range(0, nrun, B)):
                 if bi % world != rank:   # another rank's batch
                     continue
-                fwd.pos.copy_(pos_all[b0:b0 + B])
+                fwd.pos.copy_(pos_all[b0 * K:(b0 + B) * K])
                 out = fwd()
                 if out.dim() != 5 or tuple(out.shape[2:]) != (pd, ph, pw):
                     raise ValueError(f"Expected 3D model output, got shape {tuple(out.shape)}")
-                preds[b0:b0 + B].copy_(out.reshape(B, P))
+                if K == 1:
+                    preds[b0:b0 + B].copy_(out.reshape(B, P))
+                else:   # the K predictions of each window, flipped back and averaged, into its row
+                    rows = out.reshape(R, P).to(torch.float32).contiguous()
+                    nat.call("l3u_window_tta_merge", rows.data_ptr(), merge_code, K, B, pd, ph, pw,
+                             nat.ptr(preds, b0 * P), nat.stream())
             impt = torch.from_numpy(imp).to(device)
             prob = torch.empty(d, h, w, device=device)
             if mask is None:
