@@ -42,7 +42,7 @@ typedef unsigned short l3u_bf16;   /* bfloat16 bit pattern (torch.bfloat16 stora
  * another.  3: l3u_norm_src.rank1, L3U_ADAMW_TICKET_INTS tickets, the l3u_sblock_* entry points
  * removed (round 3); the round-4 entry points.  5: l3u_pw_bwd_chunk (round 6).  Added since
  * without a new version (additive, nothing existing changed): l3u_window_occupancy,
- * l3u_window_blend_masked, l3u_window_gather_flip, l3u_window_tta_merge. */
+ * l3u_window_blend_masked, l3u_window_gather_flip, l3u_window_tta_merge, l3u_resample. */
 #define L3U_ABI_VERSION 5
 int l3u_abi_version(void);
 
@@ -1028,6 +1028,29 @@ int l3u_loc_count(const void* label, int label_dtype, const unsigned char* body,
 int l3u_loc_select(const void* label, int label_dtype, const unsigned char* body, int D, int H,
                    int W, const unsigned int* prefix, int cls, const long long* ranks, int R,
                    int case_idx, int* rows, hipStream_t stream);
+
+/* ---- resampling a case to another grid (csrc/resample.hip; light_unet/resample.py) ----
+ * l3u_resample: dst[oD][oH][oW] from src[D][H][W] with the semantics of
+ * scipy.ndimage.zoom(src, zoom, order = order, mode = "nearest", grid_mode = True): output index o
+ * of an axis with n_in source and n_out output samples reads the source coordinate
+ * c = (o + 0.5) * (n_in / n_out) - 0.5 (float64, not clamped).  The caller evaluates that, per
+ * axis, into device tables of oD + oH + oW entries each (axis 0 first, then axis 1, then axis 2):
+ *   order 0: lo[i] = clamp(floor(c + 0.5), 0, n_in - 1); hi and t are not read (may be NULL).
+ *            dst[o] = src[lo], copied; dst_dtype == src_dtype, 0 float, 1 double or 2 uint8
+ *            (l3u_pp_pack's codes).
+ *   order 1: f = floor(c): lo[i] = clamp(f, 0, n_in - 1), hi[i] = clamp(f + 1, 0, n_in - 1),
+ *            t[i] = c - f.  dst (dst_dtype 0, float) from src of dtype 0 or 1: the float64 sum over
+ *            the 8 corners in C order (axis 0 the slowest bit, the low corner first) of
+ *            (((double)src * w0) * w1) * w2, w = 1 - t at a low corner and t at a high one, every
+ *            operation rounded on its own (no fused multiply-add), rounded once to float: scipy's
+ *            own operation order, so the result is scipy's bit for bit.
+ * With equal shapes every t is 0 and dst is src (rounded to float for a double source) bit for bit,
+ * for finite values other than -0 (which comes back as +0).  Table indices outside the source are
+ * clamped again on load: nothing outside src is read.  No atomics: the result is deterministic.
+ * src != dst; any other dtype pairing or order returns hipErrorInvalidValue before any launch. */
+int l3u_resample(const void* src, int src_dtype, int D, int H, int W, void* dst, int dst_dtype,
+                 int oD, int oH, int oW, int order, const int* lo, const int* hi, const double* t,
+                 hipStream_t stream);
 
 #ifdef __cplusplus
 }

@@ -144,6 +144,8 @@ _SIGS = {
     "l3u_loc_nblocks": [L],
     "l3u_loc_count": [P, I, P, L, P, P],
     "l3u_loc_select": [P, I, P, I, I, I, P, I, P, I, I, P, P],
+    # resampling to another grid: (src, dtype, D, H, W, dst, dtype, oD, oH, oW, order, lo, hi, t)
+    "l3u_resample": [P, I, I, I, I, P, I, I, I, I, I, P, P, P, P],
 }
 # entry points with a _bf16 twin (same arguments; saved activations stored as bf16, gradients
 # fp32, include/l3u.h)

@@ -7,12 +7,15 @@ mask goes into the sliding window (windows outside it are not run, utils.py `bod
 masked map stays on the device for lesion.extract_bboxes and is downloaded once, for the caller
 to save.  Reading the NIfTI image / mask and writing the map and the JSON stay with the caller.
 """
+import math
+
 from . import lesion
+from . import resample
 from .utils import sliding_window_inference_3d
 
 
 def infer_volume(image, model, config, body_mask=None, spacing=(4.0, 4.0, 4.0), threshold=None,
-                 forward_cache=None, tta_flips=None):
+                 forward_cache=None, tta_flips=None, native_shape=None):
     """(prob_map, bboxes) of one case: prob_map the float32 numpy [D, H, W] map the reference
     saves (times `body_mask` when config["data"]["body_mask"] has both `enabled` and
     `apply_to_inference`, inferencer.py:136-137, :161-162; otherwise the mask is ignored), bboxes
@@ -22,7 +25,14 @@ def infer_volume(image, model, config, body_mask=None, spacing=(4.0, 4.0, 4.0), 
     (preprocess_volume(output="device") feeds this with no host pass); `forward_cache` as in
     sliding_window_inference_3d.  The mask's dtype is one the sliding window takes (the reference
     loads it as bool); any other raises its ValueError.  `tta_flips` (default off) is the sliding
-    window's mirror test-time augmentation: None, "all" or the window axes to flip."""
+    window's mirror test-time augmentation: None, "all" or the window axes to flip.
+
+    `native_shape` (default None: nothing changes) is the way back for a case that was resampled
+    to the network's grid (preprocess_volume(target_spacing=...)): the masked map is resampled to
+    that [D, H, W] shape on the device (resample.resample_volume, order 1) and the boxes are
+    extracted there, so prob_map and bbox_voxel are on the scanner's grid and `spacing` is the
+    native one: the volume threshold converts through it, and the boxes grow by
+    ceil(data.bbox_expansion_mm / spacing[a]) voxels on axis a (at 4 mm the reference's 3)."""
     data = config["data"]
     bm = config.get("data", {}).get("body_mask", {})
     apply_mask = bm.get("apply_to_inference", False) and bm.get("enabled", False)
@@ -35,7 +45,11 @@ def infer_volume(image, model, config, body_mask=None, spacing=(4.0, 4.0, 4.0), 
                                        device=device, use_gaussian=True, output="device",
                                        forward_cache=forward_cache, body_mask=mask,
                                        tta_flips=tta_flips)
+    expansion = data["bbox_expansion_voxels"]
+    if native_shape is not None:
+        prob = resample.resample_volume(prob, native_shape, order=1, output="device")
+        expansion = [int(math.ceil(data["bbox_expansion_mm"] / s)) for s in spacing]
     bboxes = lesion.extract_bboxes(prob, threshold=threshold,
                                    min_volume_cc=data["volume_threshold"]["inference_cc"],
-                                   spacing=spacing, expansion_voxels=data["bbox_expansion_voxels"])
+                                   spacing=spacing, expansion_voxels=expansion)
     return prob.cpu().numpy(), bboxes   # the one download

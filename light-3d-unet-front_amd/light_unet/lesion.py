@@ -558,11 +558,19 @@ def extract_bboxes(prob_map, threshold=0.3, min_volume_cc=0.5, spacing=(4.0, 4.0
                    expansion_voxels=0):
     """inferencer.py:62-111 (Inferencer.extract_bboxes, with config["data"]["bbox_expansion_voxels"]
     as an argument): one box per component of (prob >= threshold) with at least
-    ceil(min_volume_cc / voxel cc) voxels, expanded and clipped to the volume."""
+    ceil(min_volume_cc / voxel cc) voxels, expanded and clipped to the volume.  expansion_voxels:
+    an int, as in the reference, or one int per axis (z, y, x) for a grid that is not isotropic."""
     pm = prob_map if isinstance(prob_map, torch.Tensor) else np.asarray(prob_map)
     shape = tuple(pm.shape)
     if len(shape) != 3:
         raise ValueError(f"extract_bboxes takes a [D, H, W] probability map, got shape {shape}")
+    if isinstance(expansion_voxels, (list, tuple, np.ndarray)):
+        if len(expansion_voxels) != 3:
+            raise ValueError("expansion_voxels takes an int or one int per axis (z, y, x), got "
+                             f"{len(expansion_voxels)} values")
+        ez, ey, ex = (int(v) for v in expansion_voxels)
+    else:
+        ez = ey = ex = expansion_voxels
     voxel_volume_cc = spacing[0] * spacing[1] * spacing[2] / 1000.0
     min_voxels = int(np.ceil(min_volume_cc / voxel_volume_cc))
     c = label(pm, threshold, min_voxels, prob=pm)
@@ -571,10 +579,9 @@ def extract_bboxes(prob_map, threshold=0.3, min_volume_cc=0.5, spacing=(4.0, 4.0
         s = c.stats[cid - 1]
         zmin, ymin, xmin = (int(v) for v in s[_MIN])
         zmax, ymax, xmax = (int(v) for v in s[_MAX])
-        e = expansion_voxels
-        zl, zh = max(0, zmin - e), min(shape[0] - 1, zmax + e)
-        yl, yh = max(0, ymin - e), min(shape[1] - 1, ymax + e)
-        xl, xh = max(0, xmin - e), min(shape[2] - 1, xmax + e)
+        zl, zh = max(0, zmin - ez), min(shape[0] - 1, zmax + ez)
+        yl, yh = max(0, ymin - ey), min(shape[1] - 1, ymax + ey)
+        xl, xh = max(0, xmin - ex), min(shape[2] - 1, xmax + ex)
         conf = (c.pmax64[cid - 1] if c.pmax64 is not None
                 else np.array([int(s[_PMAX])], dtype=np.uint32).view(np.float32)[0])
         out.append({"mask_id": cid,

@@ -24,6 +24,7 @@ import torch
 
 from . import _native as nat
 from . import lesion
+from . import resample
 
 _PACK_DTYPE = {torch.float32: 0, torch.float64: 1, torch.uint8: 2, torch.int32: 3}
 
@@ -306,15 +307,40 @@ def calculate_voxel_thresholds(spacing, volume_cc_list):
     return thresholds
 
 
-def preprocess_volume(image, config, spacing=None, output="numpy"):
+def preprocess_volume(image, config, spacing=None, output="numpy", target_spacing=None):
     """One case of preprocess_case (preprocess_data.py:243-294) without the file I/O:
     (normalized float32 -- what the reference writes to disk --, body mask or None, metadata with
     clip_values, normalization_range, body_mask when enabled and voxel_thresholds when `spacing`
     is given).  The volume is uploaded once, the initial mask comes out of the normalise launch
     (compared in float64, before the rounding to float32), and only the requested outputs and
     O(1) statistics return to the host.  config: the reference preprocessing config's
-    `intensity`, `body_mask` and `volume_threshold` sections."""
+    `intensity`, `body_mask` and `volume_threshold` sections.
+
+    `target_spacing` (default None: nothing changes) puts the case on the network's grid first,
+    where the reference only warns: with `spacing` (required then, one value per array axis) not
+    np.allclose(spacing, target_spacing, atol=0.1), the uploaded image is resampled on the device
+    (resample.resample_volume, order 1, to float32) to resample.resampled_shape(...), and the
+    percentiles, the normalisation and the body mask run on the resampled volume;
+    voxel_thresholds then use the grid's real spacing (target_spacing when resampled, else
+    spacing).  metadata["resample"] = {"orig_shape", "orig_spacing", "shape", "spacing",
+    "applied"}.  The label is the caller's to resample, to the same shape and with order 0:
+    resample_volume(label, metadata["resample"]["shape"], order=0, output="device")."""
+    if target_spacing is not None and spacing is None:
+        raise ValueError("target_spacing needs the image's spacing")
     vol = _volume(image, _device())
+    rs_meta = None
+    if target_spacing is not None:
+        orig_shape = tuple(int(v) for v in vol.shape)
+        new_shape = resample.resampled_shape(orig_shape, spacing, target_spacing)
+        applied = not np.allclose(spacing, target_spacing, atol=0.1)
+        if applied:
+            vol = resample.resample_volume(vol, new_shape, order=1, output="device")
+        rs_meta = {"orig_shape": list(orig_shape), "orig_spacing": [float(s) for s in spacing],
+                   "shape": list(new_shape if applied else orig_shape),
+                   "spacing": [float(s) for s in (target_spacing if applied else spacing)],
+                   "applied": bool(applied)}
+        if applied:
+            spacing = target_spacing
     inten = config["intensity"]
     low, high = inten["clip_percentile_low"], inten["clip_percentile_high"]
     target_range = inten["normalization_range"]
@@ -331,4 +357,6 @@ def preprocess_volume(image, config, spacing=None, output="numpy"):
         vt = config["volume_threshold"]
         meta["voxel_thresholds"] = calculate_voxel_thresholds(
             spacing, [vt["train_cc"], vt["inference_cc"]])
+    if rs_meta is not None:
+        meta["resample"] = rs_meta
     return _out(o32, output), mask, meta
