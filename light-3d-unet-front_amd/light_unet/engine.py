@@ -26,31 +26,33 @@ F32 = 4
 _FRONT = os.environ.get("L3U_FRONT", "1") != "0"
 # a block's shortcut and conv1.pointwise GEMMs as one paired launch; L3U_PAIR_PW=0 disables
 _PAIR_PW = os.environ.get("L3U_PAIR_PW", "1") != "0"
-# outputs per reduction item by partial-list length (<= 128, <= 384, longer); measured best of
-# 32..256 on the 48^3 step (tools/seg_caps.sh); L3U_SEG_CAPS overrides
 # block-tail backward inside the pointwise backwards (l3u_pw_bwd_tail); L3U_TAIL_FUSE=0 disables
 _TAIL_FUSE = os.environ.get("L3U_TAIL_FUSE", "1") != "0"
-# (an optional fourth value applies to lists longer than 1024 -- the 48^3 pointwise partials,
-# 1728 per layer: round 5 measured 8 outputs per item there +2.6 us on the reduction launch);
+# outputs per reduction item by partial-list length (<= 128, <= 384, longer); measured best of
+# 32..256 on the 48^3 step (tools/seg_caps.sh); L3U_SEG_CAPS overrides (an optional fourth value
+# applies to lists longer than 1024 -- the 48^3 pointwise partials, 1728 per layer: round 5
+# measured 8 outputs per item there +2.6 us on the reduction launch)
+_SEG_CAPS = tuple(int(v) for v in os.environ.get("L3U_SEG_CAPS", "128,64,32").split(","))
 # lists of <= 32 partials take 256 outputs per item (fewer workgroups: -3 us, r5p); L3U_SEG_SHORT
 # = <max count>:<outputs> overrides
-_SEG_CAPS = tuple(int(v) for v in os.environ.get("L3U_SEG_CAPS", "128,64,32").split(","))
 _SEG_SHORT = tuple(int(v) for v in os.environ.get("L3U_SEG_SHORT", "32:256").split(":"))
-# conv2 (depthwise + pointwise, InstanceNorm1 on load) as one l3u_dwpw_fwd launch for volumes of
-# at least this many voxels (the 48^3 level; at 24^3 its 1024-thread slabs are too few to fill
-# the chip, tools/dwpw_bench.py); L3U_DWPW=0 disables
+# conv2 (depthwise + pointwise, InstanceNorm1 on load) as one l3u_dwpw_fwd launch; L3U_DWPW=0
+# disables
 _DWPW = os.environ.get("L3U_DWPW", "1") != "0"
-# a block's conv2.pointwise and shortcut backwards as one launch at the 12^3 / 6^3 levels
-# (l3u_pw_bwd2); L3U_PAIR_BWD=0 keeps them separate
-_PAIR_BWD = os.environ.get("L3U_PAIR_BWD", "1") != "0"
-# ... and the fused block tail's two pointwise backwards (l3u_pw_bwd_tail_pair) up to this volume
-# (48^3: -35 us/step at config 2; at config 5's 64^3 the pair and the accumulating depthwise
-# backward cost +100 us, tools/run_evidence.sh step lists) and K ratio (the pair shares one
-# column-block width)
-_PAIR_TAIL_MAX_S = int(os.environ.get("L3U_PAIR_TAIL_MAX_S", str(48 ** 3)))
-# ... and for single-column-block blocks of any channel ratio (the first block's 1 -> 16)
-_PAIR_TAIL_NARROW = os.environ.get("L3U_PAIR_TAIL_NARROW", "1") != "0"
+# ... for volumes of at least this many voxels (the 48^3 level; at 24^3 its 1024-thread slabs are
+# too few to fill the chip, tools/dwpw_bench.py)
 _DWPW_MIN_S = int(os.environ.get("L3U_DWPW_MIN_S", "65536"))
+# a block's conv2.pointwise and shortcut backwards as one launch at the 12^3 / 6^3 levels
+# (l3u_pw_bwd2), and the fused block tail's two pointwise backwards as one
+# (l3u_pw_bwd_tail_pair); L3U_PAIR_BWD=0 keeps them separate
+_PAIR_BWD = os.environ.get("L3U_PAIR_BWD", "1") != "0"
+# l3u_pw_bwd_tail_pair runs up to this volume (48^3: -35 us/step at config 2; at config 5's 64^3
+# the pair and the accumulating depthwise backward cost +100 us, tools/run_evidence.sh step
+# lists) and up to a K ratio of 2 (the pair shares one column-block width)
+_PAIR_TAIL_MAX_S = int(os.environ.get("L3U_PAIR_TAIL_MAX_S", str(48 ** 3)))
+# ... and for single-column-block blocks of any channel ratio (the first block's 1 -> 16);
+# L3U_PAIR_TAIL_NARROW=0 disables
+_PAIR_TAIL_NARROW = os.environ.get("L3U_PAIR_TAIL_NARROW", "1") != "0"
 # the out_conv backward hands the last block d(pre-sigmoid) and w (out_conv is rank-1) instead
 # of the [N, C, S] output gradient (l3u_outconv_bwd_dz + the _r1 tail kernels); L3U_RANK1=0
 # disables
@@ -66,8 +68,6 @@ _FRONT_R1 = os.environ.get("L3U_FRONT_R1", "1") != "0"
 # parameters it produces (l3u_reduce_segments_adamw: no separate l3u_adamw_tick launch);
 # L3U_FUSE_ADAMW=0 keeps the two launches
 _FUSE_ADAMW = os.environ.get("L3U_FUSE_ADAMW", "1") != "0"
-
-
 # reduction items launched longest first (their workgroups start before the short items fill
 # the chip, instead of starting last); L3U_SEG_SORT=0 keeps the recording order
 _SEG_SORT = os.environ.get("L3U_SEG_SORT", "1") != "0"
@@ -112,6 +112,48 @@ class V:
     @property
     def sns(self):
         return -self.ns if self.scale is not None else self.ns
+
+    def formed(self, S):
+        """This view as a block's output gradient over S voxels, for the kernels that form it on
+        load: (entry-point suffix, leading arguments, trailing shape arguments, the six arguments
+        after (p, ns) in l3u_pw_bwd_tail_pair's packing).  The three forms: a plain tensor; rank-1
+        (w[c] * dz, l3u_outconv_bwd_dz); the skip gradient plus the folded MaxPool3d backward."""
+        if self.scale is not None:
+            return "_r1", (self.p, self.ns, self.scale), (S,), (self.scale, None, 0, None, 0, 0)
+        if self.pool is not None:
+            dpool, idx, (d, h, w) = self.pool
+            up = (dpool.data_ptr(), self.C * (S // 8), idx.data_ptr())
+            return "_up", (self.p, self.ns) + up, (d, h, w), (None,) + up + (h, w)
+        return "", (self.p, self.ns), (S,), (None, None, 0, None, 0, 0)
+
+
+class LossHead:
+    """The loss that rides in the out_conv launches.  The forward launch writes the first-stage
+    partials of (p, target) into `part` (`nparts` rows of 3 floats for FocalTversky, of 4 for the
+    family); the backward launch forms dL/dp from the global `sums` ([3] or [4] fp64) or, when
+    sums is None, reduces the partials itself, and writes the loss value into `out` when given.
+    Exactly one of `ftl` = (alpha, beta, gamma, smooth) and `family` = the nine descriptor
+    scalars (losses.family_descriptor: CombinedLoss / DiceLoss) is set."""
+    __slots__ = ("target", "part", "nparts", "sums", "out", "ftl", "family")
+
+    def __init__(self, target, part, nparts, sums=None, out=None, ftl=None, family=None):
+        if (ftl is None) == (family is None):
+            raise ValueError("a loss head is FocalTversky (ftl) or a family descriptor, not both")
+        self.target, self.part, self.nparts, self.sums = target, part, nparts, sums
+        self.out, self.ftl, self.family = out, ftl, family
+
+    def outconv_bwd(self, p):
+        """(entry-point suffix, leading arguments) of the l3u_outconv_bwd* form of this head."""
+        pt = (p.data_ptr(), self.target.data_ptr())
+        if self.sums is not None:
+            src = (self.sums.data_ptr(),)
+        else:
+            src = (self.part.data_ptr(), self.nparts)
+        if self.family is not None:
+            return "_loss4" if self.sums is not None else "_loss4p", pt + src + tuple(self.family)
+        if self.sums is not None:   # the plain entry point: its first argument is a given dL/dp
+            return "", (None,) + pt + src + tuple(self.ftl)
+        return "_ftl", pt + src + tuple(self.ftl)
 
 
 def conv_kinds(cin, cout, use_depthwise_separable=True, use_grouped=True, groups=8):
@@ -354,35 +396,38 @@ class UNetEngine:
         return tuple(d // 2 for d in diff)
 
     # ------------------------------------------------------------------ forward
-    def forward(self, flat, x, training=False, dropout_p=0.0, counter=None, save=True, target=None,
-                ftl_part=None, bump_counter=True, loss4=False):
-        """x: [N,1,D,H,W] fp32 on device -> probabilities [N,1,D,H,W] (+ saved state).  With a
-        target (same shape) the out_conv launch also writes the FocalTversky partials into
-        ftl_part [N * l3u_outconv_nblocks(S)][3]; loss4: the loss family's four-column partials
-        [..][4] (l3u_outconv_fwd_loss4: CombinedLoss / DiceLoss)."""
+    def _planned(self, key, arena, dev, impl):
+        """impl() with `arena` on the tensor self._arenas[key].  On the first use of a key a dry
+        run of impl() (every allocation and arena request, no launch) sizes that tensor first."""
+        if key not in self._arenas:
+            self._dry = True
+            arena.reset(None)
+            try:
+                impl()
+            finally:
+                self._dry = False
+            self._arenas[key] = torch.empty(max(arena.top, 64), dtype=torch.float32, device=dev)
+        arena.reset(self._arenas[key])
+        return impl()
+
+    def forward(self, flat, x, training=False, dropout_p=0.0, counter=None, save=True, loss=None,
+                bump_counter=True):
+        """x: [N,1,D,H,W] fp32 on device -> probabilities [N,1,D,H,W] (+ saved state when save).
+        training: Dropout3d with dropout_p, its masks drawn from (seed, counter); bump_counter
+        advances the counter first (False: the caller's update launch does).
+        loss: a LossHead; the out_conv launch then also writes the first-stage partials of
+        (p, loss.target) into loss.part, [N * l3u_outconv_nblocks(S)] rows of 3 (FocalTversky) or
+        4 (loss.family: l3u_outconv_fwd_loss4)."""
         self.check_shape(x)
         x = x.contiguous()
         if x.dtype != torch.float32:
             raise NotImplementedError("the network input is fp32 (bf16 storage is internal)")
         N, _, D, H, W = x.shape
-        dev = x.device
-        key = ("f", N, D, H, W, self.act_dtype)
-        if key not in self._arenas:
-            self._dry = True
-            self.fwd_arena.reset(None)
-            try:
-                self._forward_impl(flat, x, training, dropout_p, counter, save, dev, target, ftl_part,
-                                   bump_counter, loss4)
-            finally:
-                self._dry = False
-            self._arenas[key] = torch.empty(max(self.fwd_arena.top, 64), dtype=torch.float32,
-                                            device=dev)
-        self.fwd_arena.reset(self._arenas[key])
-        return self._forward_impl(flat, x, training, dropout_p, counter, save, dev, target, ftl_part,
-                                  bump_counter, loss4)
+        return self._planned(("f", N, D, H, W, self.act_dtype), self.fwd_arena, x.device,
+                             lambda: self._forward_impl(flat, x, training, dropout_p, counter, save,
+                                                        x.device, loss, bump_counter))
 
-    def _forward_impl(self, flat, x, training, dropout_p, counter, save, dev, target=None,
-                      ftl_part=None, bump_counter=True, loss4=False):
+    def _forward_impl(self, flat, x, training, dropout_p, counter, save, dev, loss, bump_counter):
         N, _, D, H, W = x.shape
         c0, c1, c2, c3 = self.enc
         dims = [(D >> k, H >> k, W >> k) for k in range(4)]
@@ -459,14 +504,12 @@ class UNetEngine:
             prev = V(out, 0, co * S[lvl], co)
         sv["ups"] = ups
         p = self._f32(N, 1, D, H, W, device=dev)   # probabilities stay fp32 (the loss input)
-        # with a target, the FocalTversky first-stage partials come out of the same launch
-        if loss4 and target is None:
-            raise ValueError("loss4 partials need a target")
-        self._call("l3u_outconv_fwd_loss4" if loss4 else "l3u_outconv_fwd", prev.p, prev.ns,
-                   self._w(flat, "out_conv.weight"),
-                   self._w(flat, "out_conv.bias"), p.data_ptr(),
-                   target.data_ptr() if target is not None else None,
-                   ftl_part.data_ptr() if target is not None else None, N, c0, S[0], st)
+        # with a loss head, its first-stage partials come out of the same launch
+        fam = loss is not None and loss.family is not None
+        self._call("l3u_outconv_fwd_loss4" if fam else "l3u_outconv_fwd", prev.p, prev.ns,
+                   self._w(flat, "out_conv.weight"), self._w(flat, "out_conv.bias"), p.data_ptr(),
+                   loss.target.data_ptr() if loss is not None else None,
+                   loss.part.data_ptr() if loss is not None else None, N, c0, S[0], st)
         sv["h"] = prev
         sv["p"] = p
         sv["blk"] = blk
@@ -555,18 +598,8 @@ class UNetEngine:
             sv["r"] = rv
             src1 = self._src(flat, pre + "norm1.", s1, nsb, rec1, drop, cptr, 1 + layer)
         else:
-            if shortcut:
-                r = e(N, cout, S)
-                so = self.fwd_arena.alloc(N * cout * nsb * 3)
-                self._call("l3u_pw_fwd", x.p, x.ns, self._w(flat, pre + "shortcut.0.weight"), 0,
-                           None, r.data_ptr(), cout * S, 0, self.fwd_arena.ptr(so), N, cin, cout, S,
-                           st)
-                src_r = self._src(flat, pre + "shortcut.1.", so, nsb, rec_r, 0.0, cptr, 0)
-                rv = V(r, 0, cout * S, cout)
-                sv["r"] = rv
-            else:
-                rv = x
-                sv["r"] = None
+            rv, src_r = self._shortcut_fwd(flat, pre, x, cout, S, rec_r, cptr, st, dev)
+            sv["r"] = rv if shortcut else None
             z1 = e(N, cin, S)
             self._call("l3u_dw3_fwd", x.p, x.ns, self._w(flat, pre + "conv1.depthwise.weight"), None,
                        None, z1.data_ptr(), cin * S, N, cin, d, h, w, st)
@@ -600,18 +633,38 @@ class UNetEngine:
                        self._w(flat, pre + "conv2.pointwise.weight"), 0, None, y2.data_ptr(), cout * S,
                        0, self.fwd_arena.ptr(s2), N, cout, cout, S, st)
         src2 = self._src(flat, pre + "norm2.", s2, nsb2, rec2, 0.0, cptr, 0)
-        if pool is None:
-            self._call("l3u_norm_act_fwd", y2.data_ptr(), cout * S, None, nat.norm_src_ptr(src2),
-                       rv.p, rv.sns, None, nat.norm_src_ptr(src_r), 1 if shortcut else 0, out.p,
-                       out.ns, N, cout, S, st)
-        else:
-            pooled, idx = pool
-            self._call("l3u_norm_act_pool_fwd", y2.data_ptr(), cout * S, None,
-                       nat.norm_src_ptr(src2), rv.p, rv.sns, None, nat.norm_src_ptr(src_r),
-                       1 if shortcut else 0, out.p, out.ns, pooled.data_ptr(), cout * (S // 8),
-                       idx.data_ptr(), N, cout, d, h, w, st)
+        self._tail_fwd(y2, src2, rv, src_r, out, pool, dims, st)
         sv.update(z1=z1, y1=y1, y1v=y1v, z2=z2, y2=y2, dims=dims, shortcut=shortcut)
         return sv
+
+    def _shortcut_fwd(self, flat, pre, x, cout, S, rec_r, cptr, st, dev):
+        """The block's residual operand and the l3u_norm_src of its InstanceNorm: the Conv1x1
+        shortcut of x in a launch of its own, or (x, None) for the identity shortcut."""
+        if not self._has(pre + "shortcut.0.weight"):
+            return x, None
+        N, cin = x.t.shape[0], x.C
+        nsb = nat.query("l3u_pw_stat_nsb", cin, cout, S)
+        r = self._empty(N, cout, S, device=dev)
+        so = self.fwd_arena.alloc(N * cout * nsb * 3)
+        self._call("l3u_pw_fwd", x.p, x.ns, self._w(flat, pre + "shortcut.0.weight"), 0, None,
+                   r.data_ptr(), cout * S, 0, self.fwd_arena.ptr(so), N, cin, cout, S, st)
+        return V(r, 0, cout * S, cout), self._src(flat, pre + "shortcut.1.", so, nsb, rec_r, 0.0,
+                                                  cptr, 0)
+
+    def _tail_fwd(self, y2, src2, rv, src_r, out, pool, dims, st):
+        """The block tail out = lrelu(IN2(y2) + IN_r(rv)) (src_r None: the identity shortcut, rv
+        added as it is); pool = (pooled, idx): also MaxPool3d(2) of out in the same launch."""
+        N, cout = y2.shape[0], out.C
+        d, h, w = dims
+        S = d * h * w
+        args = (y2.data_ptr(), cout * S, None, nat.norm_src_ptr(src2), rv.p, rv.sns, None,
+                nat.norm_src_ptr(src_r), 0 if src_r is None else 1, out.p, out.ns)
+        if pool is None:
+            self._call("l3u_norm_act_fwd", *args, N, cout, S, st)
+        else:
+            pooled, idx = pool
+            self._call("l3u_norm_act_pool_fwd", *args, pooled.data_ptr(), cout * (S // 8),
+                       idx.data_ptr(), N, cout, d, h, w, st)
 
     @staticmethod
     def _use_dwpw(cout, dims):
@@ -650,24 +703,13 @@ class UNetEngine:
         S = d * h * w
         cin, cout = x.C, out.C
         e = lambda *s: self._empty(*s, device=dev)  # noqa: E731
-        nsb = nat.query("l3u_pw_stat_nsb", cin, cout, S)
         nbg = nat.query("l3u_gconv3_nblocks", S)
         recs = self._f32(3, N * cout, 8, device=dev)
         rec_r, rec1, rec2 = (recs[0].data_ptr(), recs[1].data_ptr(), recs[2].data_ptr())
         sv = {"x": x, "out": out, "recs": recs}
         shortcut = self._has(pre + "shortcut.0.weight")
-        src_r = None
-        if shortcut:
-            r = e(N, cout, S)
-            so = self.fwd_arena.alloc(N * cout * nsb * 3)
-            self._call("l3u_pw_fwd", x.p, x.ns, self._w(flat, pre + "shortcut.0.weight"), 0, None,
-                       r.data_ptr(), cout * S, 0, self.fwd_arena.ptr(so), N, cin, cout, S, st)
-            src_r = self._src(flat, pre + "shortcut.1.", so, nsb, rec_r, 0.0, cptr, 0)
-            rv = V(r, 0, cout * S, cout)
-            sv["r"] = rv
-        else:
-            rv = x
-            sv["r"] = None
+        rv, src_r = self._shortcut_fwd(flat, pre, x, cout, S, rec_r, cptr, st, dev)
+        sv["r"] = rv if shortcut else None
         _, w1, g1 = self._conv_w(flat, pre, 1)
         _, w2, g2 = self._conv_w(flat, pre, 2)
         y1 = e(N, cout, S)
@@ -682,62 +724,44 @@ class UNetEngine:
         self._call("l3u_gconv3_fwd", y1.data_ptr(), cout * S, w2, rec1, y2.data_ptr(), cout * S,
                    self.fwd_arena.ptr(s2), N, cout, cout, g2, d, h, w, st)
         src2 = self._src(flat, pre + "norm2.", s2, nbg, rec2, 0.0, cptr, 0)
-        if pool is None:
-            self._call("l3u_norm_act_fwd", y2.data_ptr(), cout * S, None, nat.norm_src_ptr(src2),
-                       rv.p, rv.ns, None, nat.norm_src_ptr(src_r), 1 if shortcut else 0, out.p,
-                       out.ns, N, cout, S, st)
-        else:
-            pooled, idx = pool
-            self._call("l3u_norm_act_pool_fwd", y2.data_ptr(), cout * S, None,
-                       nat.norm_src_ptr(src2), rv.p, rv.ns, None, nat.norm_src_ptr(src_r),
-                       1 if shortcut else 0, out.p, out.ns, pooled.data_ptr(), cout * (S // 8),
-                       idx.data_ptr(), N, cout, d, h, w, st)
+        self._tail_fwd(y2, src2, rv, src_r, out, pool, dims, st)
         sv.update(y1=y1, y2=y2, dims=dims, shortcut=shortcut)
         return sv
 
     # ------------------------------------------------------------------ backward
-    def backward(self, flat, gflat, sv, dp, need_dx=False, ftl=None, opt=None, family=None):
-        """Given dL/dp write all parameter gradients into gflat (overwrite) and return dL/dx if
-        need_dx.  opt: the FlatAdamW over (flat, gflat) of a one-process step; when the gradient
-        reduction covers every parameter once, its launch also applies the update and
-        self.applied_update is True (the caller must then not call opt.step()).  dp = None: the loss is FocalTversky and ftl = (target, global sums [3] fp64,
-        (alpha, beta, gamma, smooth)[, loss tensor[, partials, n_partials]]); its gradient is
-        formed inside the out_conv backward, which also writes the loss value when a loss tensor
-        is given.  sums = None: the out_conv backward reduces the forward's FocalTversky
-        partials itself (l3u_outconv_bwd_ftl; no reduce launch).
-        family: the nine loss-family descriptor scalars (losses.family_descriptor) for
-        CombinedLoss / DiceLoss; `ftl` then holds (target, sums [4] or None, None, loss tensor[,
-        four-column partials, n_partials]) and the l3u_outconv_bwd_loss4* forms run.  family =
-        None issues exactly the FocalTversky calls."""
+    def backward(self, flat, gflat, sv, dp, need_dx=False, loss=None, opt=None):
+        """Write all parameter gradients into gflat (overwrite) and return dL/dx if need_dx.
+        sv: the saved state of forward().  Either dp = dL/dp is given, or dp is None and `loss`
+        is the LossHead of the forward: the out_conv backward then forms dL/dp itself, from
+        loss.sums or (loss.sums None) from the forward's partials, which it reduces in the same
+        launch, and writes the loss value into loss.out.
+        opt: the FlatAdamW over (flat, gflat) of a one-process step; when the gradient reduction
+        covers every parameter once, its launch also applies the update and self.applied_update
+        is True (the caller must then not call opt.step())."""
         N = sv["N"]
         D, H, W = sv["dims"][0]
         self.set_act_dtype(sv["adt"])
         key = ("b", N, D, H, W, bool(need_dx), self.act_dtype)
+        dev = sv["p"].device
+        first = key not in self._arenas
+        if first:
+            self.seg_bytes = {}
+
+        def impl():
+            self._items_rec = []
+            return self._backward_impl(flat, sv, dp, need_dx, loss)
         self._grad_phase = True
         try:
-            if key not in self._arenas:
-                self._dry = True
-                self.bwd_arena.reset(None)
-                self._items_rec = []
-                self.seg_bytes = {}
-                try:
-                    self._backward_impl(flat, gflat, sv, dp, need_dx, ftl, family)
-                finally:
-                    self._dry = False
-                dev = sv["p"].device
-                self._arenas[key] = torch.empty(max(self.bwd_arena.top, 64), dtype=torch.float32,
-                                                device=dev)
-                # items are independent (each output is written by one item), so their order
-                # changes no result
-                rec = sorted(self._items_rec, key=lambda it: -_seg_rounds(it)) if _SEG_SORT \
-                    else self._items_rec
-                self._items[key] = torch.tensor(rec, dtype=torch.int64, device=dev)
-                self._cover_once[key] = _items_cover_once(self._items_rec, gflat.numel())
-            self.bwd_arena.reset(self._arenas[key])
-            self._items_rec = []
-            dx = self._backward_impl(flat, gflat, sv, dp, need_dx, ftl, family)
+            dx = self._planned(key, self.bwd_arena, dev, impl)
         finally:
             self._grad_phase = False
+        if first:
+            # items are independent (each output is written by one item), so their order
+            # changes no result
+            rec = sorted(self._items_rec, key=lambda it: -_seg_rounds(it)) if _SEG_SORT \
+                else self._items_rec
+            self._items[key] = torch.tensor(rec, dtype=torch.int64, device=dev)
+            self._cover_once[key] = _items_cover_once(self._items_rec, gflat.numel())
         items = self._items[key]
         self.applied_update = (opt is not None and _FUSE_ADAMW and self._cover_once[key]
                                and opt.g is gflat and opt.p is flat)
@@ -749,7 +773,7 @@ class UNetEngine:
                      items.shape[0], gflat.data_ptr(), nat.stream())
         return dx
 
-    def _backward_impl(self, flat, gflat, sv, dp, need_dx, ftl=None, family=None):
+    def _backward_impl(self, flat, sv, dp, need_dx, loss):
         N = sv["N"]
         dims, S = sv["dims"], sv["S"]
         c0, c1, c2, c3 = self.enc
@@ -763,44 +787,18 @@ class UNetEngine:
         # rank-1 hand-off: the tail kernels of the last block form dout[c] = w[c] * dz themselves
         r1 = _RANK1 and self.kinds["up3.res_block."][0][0] == "ds" and \
             self._tail_fusable(up3, up3["x"].C, c0, S[0])
-        sfx = "_dz" if r1 else ""
         dh = e(N, 1, S[0]) if r1 else e(N, c0, S[0])
         dhns = S[0] if r1 else c0 * S[0]
         nb = nat.query("l3u_outconv_nblocks", S[0])
         po = A.alloc(2 * N * nb * (c0 + 1))          # fp64 partials
-        loss_ptr = None
-        if dp is not None:
-            g = (dp.data_ptr(), None, None, 0.0, 0.0, 0.0, 0.0, None)
-            self._call("l3u_outconv_bwd" + sfx, g[0], sv["p"].data_ptr(), *g[1:], h.p, h.ns,
-                       self._w(flat, "out_conv.weight"), dh.data_ptr(), dhns, A.ptr(po),
-                       loss_ptr, N, c0, S[0], st)
-        elif family is not None:   # the loss family's gradient from the four global sums
-            t, sums = ftl[:2]
-            if len(ftl) > 3 and ftl[3] is not None:
-                loss_ptr = ftl[3].data_ptr()
-            tail = (None, h.p, h.ns, self._w(flat, "out_conv.weight"), dh.data_ptr(), dhns,
-                    A.ptr(po), loss_ptr, N, c0, S[0], st)
-            if sums is None:   # reduced inside the launch from the forward's partials
-                self._call("l3u_outconv_bwd_loss4p" + sfx, sv["p"].data_ptr(), t.data_ptr(),
-                           ftl[4].data_ptr(), ftl[5], *family, *tail)
-            else:
-                self._call("l3u_outconv_bwd_loss4" + sfx, sv["p"].data_ptr(), t.data_ptr(),
-                           sums.data_ptr(), *family, *tail)
-        else:   # FocalTversky gradient formed inside the kernel from the global sums
-            t, sums, (alpha, beta, gamma, smooth) = ftl[:3]
-            if len(ftl) > 3 and ftl[3] is not None:   # the loss value, written by the same launch
-                loss_ptr = ftl[3].data_ptr()
-            if sums is None:   # the sums reduced inside the launch from the forward's partials
-                fpart, fnp = ftl[4], ftl[5]
-                self._call("l3u_outconv_bwd_ftl" + sfx, sv["p"].data_ptr(), t.data_ptr(),
-                           fpart.data_ptr(), fnp, alpha, beta, gamma, smooth, None, h.p, h.ns,
-                           self._w(flat, "out_conv.weight"), dh.data_ptr(), dhns, A.ptr(po),
-                           loss_ptr, N, c0, S[0], st)
-            else:
-                self._call("l3u_outconv_bwd" + sfx, None, sv["p"].data_ptr(), t.data_ptr(),
-                           sums.data_ptr(), alpha, beta, gamma, smooth, None, h.p, h.ns,
-                           self._w(flat, "out_conv.weight"), dh.data_ptr(), dhns, A.ptr(po),
-                           loss_ptr, N, c0, S[0], st)
+        if dp is not None:   # the plain entry point on a given dL/dp: no target, sums or scalars
+            form, lead = "", (dp.data_ptr(), sv["p"].data_ptr(), None, None, 0.0, 0.0, 0.0, 0.0)
+        else:                # dL/dp formed in the launch, which also writes the loss value
+            form, lead = loss.outconv_bwd(sv["p"])
+        out = None if dp is not None or loss.out is None else loss.out.data_ptr()
+        self._call("l3u_outconv_bwd" + form + ("_dz" if r1 else ""), *lead, None, h.p, h.ns,
+                   self._w(flat, "out_conv.weight"), dh.data_ptr(), dhns, A.ptr(po), out, N, c0,
+                   S[0], st)
         self._seg(po // 2, N * nb, c0 + 1, 1, c0, "out_conv.weight", f64=1)
         self._seg(po // 2 + c0, N * nb, c0 + 1, 1, 1, "out_conv.bias", f64=1)
         dcat3, dcat2, dcat1 = e(N, 2 * c0, S[0]), e(N, 2 * c1, S[1]), e(N, 2 * c2, S[2])
@@ -826,22 +824,18 @@ class UNetEngine:
                 self._call32("l3u_box_copy", dY, dYns, *dims[lvl], dup.data_ptr(), co * 8 * S[lvl + 1],
                              2 * d, 2 * hh, 2 * w, *[-o for o in pad], N, co, st)
                 dY, dYns = dup.data_ptr(), co * 8 * S[lvl + 1]
-            npf = nat.query("l3u_convt_bwd_fused_nparts", N, ci, co, d, hh, w)
-            if npf > 0:   # one launch: data, weight and bias gradients
-                pw, pb = A.alloc(npf * ci * co * 8), A.alloc(npf * co)
-                self._call("l3u_convt_bwd_fused", dY, dYns, prev.p, prev.ns,
-                           self._w(flat, up + "up.weight"), dprev.data_ptr(), ci * S[lvl + 1],
-                           A.ptr(pw), A.ptr(pb), N, ci, co, d, hh, w, st)
-                self._seg(pw, npf, ci * co * 8, 1, ci * co * 8, up + "up.weight")
-                self._seg(pb, npf, co, 1, co, up + "up.bias")
-            else:
+            # data, weight and bias gradients: l3u_convt_bwd_fused where it takes the shape (it
+            # reports its own partial count), else l3u_convt_bwd
+            npw = nat.query("l3u_convt_bwd_fused_nparts", N, ci, co, d, hh, w)
+            name = "l3u_convt_bwd_fused" if npw > 0 else "l3u_convt_bwd"
+            if npw <= 0:
                 npw = nat.query("l3u_pw_bwd_weight_nparts", N, S[lvl + 1])
-                pw, pb = A.alloc(npw * ci * co * 8), A.alloc(npw * co)
-                self._call("l3u_convt_bwd", dY, dYns, prev.p, prev.ns,
-                           self._w(flat, up + "up.weight"), dprev.data_ptr(), ci * S[lvl + 1],
-                           A.ptr(pw), A.ptr(pb), N, ci, co, d, hh, w, st)
-                self._seg(pw, npw, ci * co * 8, 1, ci * co * 8, up + "up.weight")
-                self._seg(pb, npw, co, 1, co, up + "up.bias")
+            pw, pb = A.alloc(npw * ci * co * 8), A.alloc(npw * co)
+            self._call(name, dY, dYns, prev.p, prev.ns, self._w(flat, up + "up.weight"),
+                       dprev.data_ptr(), ci * S[lvl + 1], A.ptr(pw), A.ptr(pb), N, ci, co, d, hh, w,
+                       st)
+            self._seg(pw, npw, ci * co * 8, 1, ci * co * 8, up + "up.weight")
+            self._seg(pb, npw, co, 1, co, up + "up.bias")
             dout = V(dprev, 0, ci * S[lvl + 1], ci)
         # ---- bottleneck
         dx4 = e(N, c3, S[3])
@@ -912,21 +906,14 @@ class UNetEngine:
         pnd = pn // 2
         self._seg(pnd + 1, N * nb, 3, N * nb * 3, cout, pre + "norm2.weight", f64=1)
         self._seg(pnd + 0, N * nb, 3, N * nb * 3, cout, pre + "norm2.bias", f64=1)
+        # the output gradient in its form (V.formed), then the operands every tail kernel reads
+        form, lead, shape, _ = dout.formed(S)
+        ops = (out.p, out.ns, y2.data_ptr(), cout * S, rec2, rv.p, rv.sns,
+               rec_r if shortcut else None, A.ptr(pn))
         if fused:
             self._seg(pnd + 2, N * nb, 3, N * nb * 3, cout, pre + "shortcut.1.weight", f64=1)
             self._seg(pnd + 0, N * nb, 3, N * nb * 3, cout, pre + "shortcut.1.bias", f64=1)
-            if dout.scale is not None:   # rank-1 dout (l3u_outconv_bwd_dz)
-                self._call("l3u_norm_act_bwd_reduce_r1", dout.p, dout.ns, dout.scale, out.p, out.ns,
-                           y2.data_ptr(), cout * S, rec2, rv.p, rv.sns, rec_r, A.ptr(pn), N, cout, S,
-                           st)
-            elif dout.pool is not None:   # skip gradient + the folded MaxPool3d backward
-                dpool, idx, (d, h, w) = dout.pool
-                self._call("l3u_norm_act_bwd_reduce_up", dout.p, dout.ns, dpool.data_ptr(),
-                           cout * (S // 8), idx.data_ptr(), out.p, out.ns, y2.data_ptr(), cout * S,
-                           rec2, rv.p, rv.sns, rec_r, A.ptr(pn), N, cout, d, h, w, st)
-            else:
-                self._call("l3u_norm_act_bwd_reduce", dout.p, dout.ns, out.p, out.ns, y2.data_ptr(),
-                           cout * S, rec2, rv.p, rv.sns, rec_r, A.ptr(pn), N, cout, S, st)
+            self._call("l3u_norm_act_bwd_reduce" + form, *lead, *ops, N, cout, *shape, st)
             return pn, nb
         assert dout.scale is None and (dout.pool is None or nb == 1), "a formed-on-load output " \
             "gradient needs the fused block tail or a one-launch plane"
@@ -939,23 +926,12 @@ class UNetEngine:
             self._seg(pnd + 0, N * nb, 3, N * nb * 3, cout, pre + "shortcut.1.bias", f64=1)
         else:
             drv = dxv   # identity shortcut: d(input) starts as g
-        if nb == 1 and dout.pool is not None:   # + the folded MaxPool3d backward
-            dpool, idx, (d, h, w) = dout.pool
-            self._call("l3u_norm_act_bwd_up", dout.p, dout.ns, dpool.data_ptr(), cout * (S // 8),
-                       idx.data_ptr(), out.p, out.ns, y2.data_ptr(), cout * S, rec2, rv.p, rv.ns,
-                       rec_r if shortcut else None, A.ptr(pn), dy2.data_ptr(), cout * S, drv.p,
-                       drv.ns, N, cout, d, h, w, st)
-            return dy2, drv
-        if nb == 1:   # one workgroup per plane: reduce and apply in one launch
-            self._call("l3u_norm_act_bwd", dout.p, dout.ns, out.p, out.ns, y2.data_ptr(), cout * S,
-                       rec2, rv.p, rv.ns, rec_r if shortcut else None, A.ptr(pn), dy2.data_ptr(),
-                       cout * S, drv.p, drv.ns, N, cout, S, st)
-            return dy2, drv
-        self._call("l3u_norm_act_bwd_reduce", dout.p, dout.ns, out.p, out.ns, y2.data_ptr(), cout * S,
-                   rec2, rv.p, rv.ns, rec_r if shortcut else None, A.ptr(pn), N, cout, S, st)
-        self._call("l3u_norm_act_bwd_apply", dout.p, dout.ns, out.p, out.ns, y2.data_ptr(), cout * S,
-                   rec2, rv.p, rv.ns, rec_r if shortcut else None, A.ptr(pn), dy2.data_ptr(),
-                   cout * S, drv.p, drv.ns, N, cout, S, st)
+        grads = (dy2.data_ptr(), cout * S, drv.p, drv.ns)
+        if nb == 1:   # one workgroup per plane: reduce and apply in one launch (plain or _up)
+            self._call("l3u_norm_act_bwd" + form, *lead, *ops, *grads, N, cout, *shape, st)
+        else:         # (a plain gradient, by the assertion above)
+            self._call("l3u_norm_act_bwd_reduce", *lead, *ops, N, cout, S, st)
+            self._call("l3u_norm_act_bwd_apply", *lead, *ops, *grads, N, cout, S, st)
         return dy2, drv
 
     def _block_bwd_g(self, flat, pre, sv, dout, dxv, st, dev):
@@ -1164,14 +1140,9 @@ class UNetEngine:
             segs.append((off, npw, J * x.C, name))
             args += [yr.p, yr.sns, rec, x.p, x.ns, self._w(flat, name), dx.p, dx.ns, 0, A.ptr(off), x.C,
                      sel]
-        dscale = dout.scale
-        if dout.pool is not None:
-            dpool, idx, (d, h, w) = dout.pool
-            pool = [dpool.data_ptr(), J * (S // 8), idx.data_ptr(), h, w]
-        else:
-            pool = [None, 0, None, 0, 0]
-        self._call("l3u_pw_bwd_tail_pair", dout.p, dout.ns, dscale, *pool, out.p, out.ns, A.ptr(pn),
-                   ntp, *args, N, J, S, st)
+        # one entry point for the three forms of dout: its scale and pool arguments, or nulls
+        self._call("l3u_pw_bwd_tail_pair", dout.p, dout.ns, *dout.formed(S)[3], out.p, out.ns,
+                   A.ptr(pn), ntp, *args, N, J, S, st)
         for off, npw, n, name in segs:
             self._seg(off, npw, n, 1, n, name)
 
@@ -1183,20 +1154,10 @@ class UNetEngine:
         A = self.bwd_arena
         npw = nat.query("l3u_pw_bwd_nparts", N, J, K, S)
         part = A.alloc(npw * J * K)
-        if dout.scale is not None:   # rank-1 dout (l3u_outconv_bwd_dz)
-            self._call("l3u_pw_bwd_tail_r1", dout.p, dout.ns, dout.scale, out.p, out.ns, yr.p, yr.sns,
-                       rec, A.ptr(pn), ntp, sel, x.p, x.ns, self._w(flat, name), dx.p, dx.ns,
-                       accumulate, A.ptr(part), N, J, K, S, st)
-        elif dout.pool is not None:   # skip gradient + the folded MaxPool3d backward
-            dpool, idx, (d, h, w) = dout.pool
-            self._call("l3u_pw_bwd_tail_up", dout.p, dout.ns, dpool.data_ptr(), J * (S // 8),
-                       idx.data_ptr(), out.p, out.ns, yr.p, yr.sns, rec, A.ptr(pn), ntp, sel, x.p,
-                       x.ns, self._w(flat, name), dx.p, dx.ns, accumulate, A.ptr(part), N, J, K, d, h,
-                       w, st)
-        else:
-            self._call("l3u_pw_bwd_tail", dout.p, dout.ns, out.p, out.ns, yr.p, yr.sns, rec,
-                       A.ptr(pn), ntp, sel, x.p, x.ns, self._w(flat, name), dx.p, dx.ns, accumulate,
-                       A.ptr(part), N, J, K, S, st)
+        form, lead, shape, _ = dout.formed(S)
+        self._call("l3u_pw_bwd_tail" + form, *lead, out.p, out.ns, yr.p, yr.sns, rec, A.ptr(pn), ntp,
+                   sel, x.p, x.ns, self._w(flat, name), dx.p, dx.ns, accumulate, A.ptr(part), N, J, K,
+                   *shape, st)
         self._seg(part, npw, J * K, 1, J * K, name)
 
     def _seg_dw(self, off, count, C, name):

@@ -24,6 +24,7 @@ import torch
 import torch.distributed as dist
 
 from . import _native as nat
+from .engine import LossHead
 from .exchange import check_mode, exchange_ftl_sums, exchange_grads, world_size
 from .models.losses import FocalTverskyLoss, family_descriptor, loss_family
 from .optim import FlatAdamW
@@ -112,52 +113,49 @@ class TrainStep:
 
     # ----------------------------------------------------------------- pieces
     def _fwd(self, x, t):
-        # the out_conv launch also produces the FocalTversky partials (losses.py:40-42)
+        """Forward; the out_conv launch also produces the loss partials (losses.py:40-42).
+        Returns (p, saved state, the step's LossHead)."""
         N, S = x.shape[0], x[0].numel()
         nparts = N * nat.query("l3u_outconv_nblocks", S)
         fam = self.family is not None
         ncol = 4 if fam else 3
         part = torch.empty(nparts * ncol, dtype=torch.float32, device=x.device)
+        head = LossHead(t, part, nparts, out=self.loss, family=self.family,
+                        ftl=None if fam else (self.alpha, self.beta, self.gamma, self.smooth))
         self.engine.set_act_dtype(self.act_dtype)
         p, sv = self.engine.forward(self.flat, x, training=self.model.training,
                                     dropout_p=self.model.dropout_p,
                                     counter=self.model._rng_counter, bump_counter=False,
-                                    save=True, target=t,
-                                    ftl_part=part, loss4=fam)
-        if not self.exchange:
-            # one process: the out_conv backward reduces the partials itself (no reduce launch)
-            return p, sv, (part, nparts)
-        sums = torch.empty(ncol, dtype=torch.float64, device=p.device)
-        nat.call("l3u_loss4_reduce" if fam else "l3u_ftl_reduce", part.data_ptr(), nparts,
-                 sums.data_ptr(), nat.stream())
-        return p, sv, sums
+                                    save=True, loss=head)
+        if self.exchange:
+            # the sums leave the device step to be exchanged; one process: the out_conv backward
+            # reduces the partials itself (no reduce launch)
+            head.sums = torch.empty(ncol, dtype=torch.float64, device=p.device)
+            nat.call("l3u_loss4_reduce" if fam else "l3u_ftl_reduce", part.data_ptr(), nparts,
+                     head.sums.data_ptr(), nat.stream())
+        return p, sv, head
 
-    def _bwd(self, p, sv, t, sums):
-        # dL/dp is formed inside the out_conv backward from t and the (global) sums; the same
-        # launch writes the loss value (losses.py:52-54)
-        abgs = (self.alpha, self.beta, self.gamma, self.smooth)
-        family = None
-        if self.family is not None:
+    def _bwd(self, p, sv, t, head):
+        """Backward (t: the target the head already carries); dL/dp is formed inside the out_conv
+        backward from the head's (global) sums or partials, and the same launch writes the loss
+        value (losses.py:52-54).  True when the update was applied as well."""
+        if head.family is not None:
             # the BCE mean runs over the elements the sums cover: all ranks' (equal) shards in
             # exact mode, this rank's own in local mode
             glob = self.world if self.exchange and self.ftl_mode == "exact" else 1
-            family = self.family[:6] + (float(p.numel() * glob),) + self.family[7:]
-        if isinstance(sums, tuple):   # (partials, count): reduced inside the out_conv backward
-            ftl = (t, None, abgs, self.loss, sums[0], sums[1])
-        else:
-            ftl = (t, sums, abgs, self.loss)
+            head.family = head.family[:6] + (float(p.numel() * glob),) + head.family[7:]
         # one process: the gradient reduction launch also applies the AdamW update
-        self.engine.backward(self.flat, self.gflat, sv, None, need_dx=False, ftl=ftl,
-                             opt=None if self.exchange else self.opt, family=family)
+        self.engine.backward(self.flat, self.gflat, sv, None, need_dx=False, loss=head,
+                             opt=None if self.exchange else self.opt)
         return self.engine.applied_update
 
     def _grad_exchange(self):
         if self.exchange:
             exchange_grads(self.gflat, self.ftl_mode, self.group, force=self.force)
 
-    def _sums_exchange(self, sums):
+    def _sums_exchange(self, head):
         if self.exchange:
-            exchange_ftl_sums(sums, self.ftl_mode, self.group, force=self.force)
+            exchange_ftl_sums(head.sums, self.ftl_mode, self.group, force=self.force)
 
     def _check_flat(self):
         if self.model._flat is not self.flat:
@@ -168,9 +166,9 @@ class TrainStep:
     def __call__(self, x, t):
         """One step on device tensors x, t [N,1,D,H,W]; returns the device loss (no sync)."""
         self._check_flat()
-        p, sv, sums = self._fwd(x, t)
-        self._sums_exchange(sums)
-        if not self._bwd(p, sv, t, sums):
+        p, sv, head = self._fwd(x, t)
+        self._sums_exchange(head)
+        if not self._bwd(p, sv, t, head):
             self._grad_exchange()
             self.opt.step()
         return self.loss
@@ -213,9 +211,9 @@ class TrainStep:
         else:
             g1, g2, g3 = torch.cuda.CUDAGraph(), torch.cuda.CUDAGraph(), torch.cuda.CUDAGraph()
             with torch.cuda.graph(g1, pool=pool, capture_error_mode=mode):
-                self._cap_p, self._cap_sv, self._cap_sums = self._fwd(self.xs, self.ts)
+                self._cap_p, self._cap_sv, self._cap_head = self._fwd(self.xs, self.ts)
             with torch.cuda.graph(g2, pool=pool, capture_error_mode=mode):
-                self._bwd(self._cap_p, self._cap_sv, self.ts, self._cap_sums)
+                self._bwd(self._cap_p, self._cap_sv, self.ts, self._cap_head)
             with torch.cuda.graph(g3, pool=pool, capture_error_mode=mode):
                 self.opt.step()
             self._graphs = [g1, g2, g3]
@@ -230,7 +228,7 @@ class TrainStep:
         else:
             g1, g2, g3 = self._graphs
             g1.replay()
-            self._sums_exchange(self._cap_sums)
+            self._sums_exchange(self._cap_head)
             g2.replay()
             self._grad_exchange()
             g3.replay()
