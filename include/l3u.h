@@ -1052,6 +1052,40 @@ int l3u_resample(const void* src, int src_dtype, int D, int H, int W, void* dst,
                  int oD, int oH, int oW, int order, const int* lo, const int* hi, const double* t,
                  hipStream_t stream);
 
+/* ---- surface-distance metrics (csrc/surface.hip; light_unet/surface.py) ----
+ * l3u_edt: the exact Euclidean distance transform of a packed feature mask (l3u_pp_pack's format,
+ * bit 1 = feature voxel) with the spacings (sz, sy, sx) > 0: out[D][H][W] (double) holds
+ *   sqrt(min over feature voxels f of fl(fl(((z-fz) sz)^2 + ((y-fy) sy)^2) + ((x-fx) sx)^2)),
+ * every product and sum rounded to double once (nothing fused), summed in z, y, x order: the
+ * arithmetic of scipy.ndimage.distance_transform_edt(~feat, sampling), whose map this is bit for
+ * bit.  Without a feature voxel every output is +inf.  Three line passes (rounding is monotone, so
+ * the float minimum separates): bit 0 of `passes` the z pass feat -> out, bit 1 the y pass
+ * out -> tmp, bit 2 the x pass and the square root tmp -> out; passes = 7 is the transform, a
+ * subset runs those passes alone on whatever the buffers hold (timing).  The y and x passes scan
+ * outwards from each voxel and stop once the squared step alone reaches the best value; the scan is
+ * bounded by the line length.  tmp: D * H * W doubles of workspace, out != tmp.
+ * D * H * W < 2^31, else hipErrorInvalidValue before any launch.
+ *
+ * l3u_surf_mask: out = in & ~erode6(in) on packed masks (6-neighbour erosion, everything outside
+ * the volume 0, so mask voxels on a volume face are surface): scipy's
+ * in & ~binary_erosion(in, generate_binary_structure(3, 1)).  in != out.
+ *
+ * l3u_surf_reduce: over the voxels of the packed mask `surf`, of the distance map dist[D][H][W]:
+ * res[11] (double) = their count, the maximum of dist (0 when there is none), the sum of dist, and
+ * for q < ntol (0..8) the count of dist <= tol[q] at res[3 + q] (tol: HOST memory, read during the
+ * call); sd[D][H][W] receives dist at surface voxels and +inf elsewhere, so that l3u_pp_select over
+ * sd reads the order statistics of the surface distances at every rank below the count.  No float
+ * atomics: part (l3u_surf_nblocks(D * H * W) * 12 doubles of workspace) takes one partial per 4096
+ * voxels of the flat order, summed in a fixed order inside the workgroup, and one wave merges the
+ * partials in a fixed order; the same input gives the same bits on every run.  dist != sd. */
+int l3u_edt(const unsigned long long* feat, double sz, double sy, double sx, double* out,
+            double* tmp, int D, int H, int W, int passes, hipStream_t stream);
+int l3u_surf_mask(const unsigned long long* in, unsigned long long* out, int D, int H, int W,
+                  hipStream_t stream);
+int l3u_surf_nblocks(long long n);
+int l3u_surf_reduce(const double* dist, const unsigned long long* surf, const double* tol, int ntol,
+                    double* sd, double* part, double* res, int D, int H, int W, hipStream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

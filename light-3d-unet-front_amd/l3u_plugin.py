@@ -52,6 +52,7 @@ def load():
     importlib.import_module(ALIAS + ".lesion")
     importlib.import_module(ALIAS + ".patches")
     importlib.import_module(ALIAS + ".preprocess")
+    importlib.import_module(ALIAS + ".surface")
     importlib.import_module(ALIAS + ".inference")
     return mod
 
@@ -181,7 +182,10 @@ def install(fast_step=False, lesion=True, device_patches=False, fast_validate=Fa
     Trainer._l3u_reference_validate.  Needs light_unet.core.trainer.  It also reads one config key
     the reference does not have, validation.tta_flips (default: absent, off): None, "all" or a
     list of window axes out of 0, 1, 2 -- the sliding window's mirror test-time augmentation
-    (light_unet/utils.py `tta_flips`).
+    (light_unet/utils.py `tta_flips`).  A second such key, validation.surface_metrics (default:
+    absent, off) = {"tolerances_mm": [...], "percentile": 95.0}, is passed to
+    lesion.sweep_metrics(surface=...): the returned metrics then carry hd95_mean, assd_mean,
+    nsd_mean and surface_cases (light_unet/surface.py).
 
     device_locations=True also replaces PatchDataset._sample_locations (patch_dataset.py:74-100):
     every case's label and body mask are read as the reference reads them and uploaded (label as

@@ -146,6 +146,12 @@ _SIGS = {
     "l3u_loc_select": [P, I, P, I, I, I, P, I, P, I, I, P, P],
     # resampling to another grid: (src, dtype, D, H, W, dst, dtype, oD, oH, oW, order, lo, hi, t)
     "l3u_resample": [P, I, I, I, I, P, I, I, I, I, I, P, P, P, P],
+    # surface distances: exact EDT of a packed mask (feat, sz, sy, sx, out, tmp, D, H, W, passes),
+    # the surface of a packed mask, and the reductions over surface voxels (tol[ntol] on the HOST)
+    "l3u_edt": [P, D, D, D, P, P, I, I, I, I, P],
+    "l3u_surf_mask": [P, P, I, I, I, P],
+    "l3u_surf_nblocks": [L],
+    "l3u_surf_reduce": [P, P, P, I, P, P, P, I, I, I, P],
 }
 # entry points with a _bf16 twin (same arguments; saved activations stored as bf16, gradients
 # fp32, include/l3u.h)
@@ -170,7 +176,7 @@ _QUERIES = {"l3u_abi_version", "l3u_dw3_nchunk", "l3u_pw_stat_nsb", "l3u_pw_bwd_
             "l3u_ccl_nchunks", "l3u_dwpw_supported", "l3u_dwpw_stat_nsb",
             "l3u_dw3_bwd_rank1", "l3u_pw_bwd2_supported", "l3u_pw_bwd_chunk",
             "l3u_ccl_lv_max_levels", "l3u_pp_select_ws_bytes", "l3u_pp_morph_max_iters",
-            "l3u_loc_nblocks"}
+            "l3u_loc_nblocks", "l3u_surf_nblocks"}
 
 LOC_BLOCK = 4096    # L3U_LOC_BLOCK
 

@@ -41,7 +41,8 @@ Trainer, so later epochs neither capture nor label the targets again.  A body ma
 with the map numpy keeps in float32 goes into the sliding window (`body_mask=`): windows outside
 it are not run and the map arrives already multiplied by it.  One config key the reference does
 not have, `validation.tta_flips` (absent: off), turns on the sliding window's mirror test-time
-augmentation.
+augmentation; another, `validation.surface_metrics` (absent: off), adds the boundary metrics of
+`light_unet/surface.py` to the returned dict (`lesion.sweep_metrics(surface=...)`).
 """
 import torch
 
@@ -262,15 +263,17 @@ def bind(trainer_cls):
 
 # ---------------------------------------------------------------------- validation
 def evaluate_maps(prob_maps, labels, spacings, thresholds, tie_threshold, is_better,
-                  body_masks=None, target_cache=None, case_keys=None):
+                  body_masks=None, target_cache=None, case_keys=None, surface=None):
     """The post-inference stage of Trainer.validate (trainer.py:423-445) on probability maps
     (numpy or device): the metrics at every threshold from one lesion.sweep_metrics call, then the
     reference's selection loop with `is_better` (the Trainer's _is_better_metric).  Returns the
-    chosen metrics dict with best_threshold / best_recall / best_dsc_macro."""
+    chosen metrics dict with best_threshold / best_recall / best_dsc_macro.  `surface` (None: off)
+    is sweep_metrics' argument of that name: the chosen dict then carries the boundary metrics."""
     thresholds = list(thresholds)
+    kw = {} if surface is None else {"surface": surface}
     swept = lesion.sweep_metrics(prob_maps, labels, thresholds, spacing=spacings,
                                  body_masks=body_masks, target_cache=target_cache,
-                                 case_keys=case_keys)
+                                 case_keys=case_keys, **kw)
     best_threshold, best_metrics = thresholds[0], swept[0]
     best_recall = best_metrics["lesion_wise_recall"]
     best_dsc_macro = best_metrics["voxel_wise_dsc_macro"]
@@ -319,6 +322,8 @@ def validate(self, epoch):
     apply_body_mask = bm.get("apply_to_validation", False) and bm.get("enabled", False)
     # mirror test-time augmentation: a key the reference configs do not have (absent: off)
     tta_flips = self.config["validation"].get("tta_flips")
+    # boundary metrics (light_unet/surface.py): another key of this build's own (absent: off)
+    surface_metrics = self.config["validation"].get("surface_metrics")
     dev = torch.device(self.device)
     with torch.no_grad():
         for batch in _tqdm(self.val_loader, desc=f"Epoch {epoch+1} [Val]"):
@@ -368,7 +373,7 @@ def validate(self, epoch):
     best = evaluate_maps(maps, all_labels, all_spacings, thresholds, tie_threshold,
                          self._is_better_metric,
                          body_masks=masks if any(m is not None for m in masks) else None,
-                         target_cache=state["targets"], case_keys=keys)
+                         target_cache=state["targets"], case_keys=keys, surface=surface_metrics)
     return 0.0, best
 
 

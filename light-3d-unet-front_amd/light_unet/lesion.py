@@ -466,7 +466,7 @@ def _sweep_case(pred, mask, tc, thr32, thr64, spacing, dev, max_workspace_bytes)
 
 
 def sweep_metrics(predictions, labels, thresholds, spacing=(4.0, 4.0, 4.0), body_masks=None,
-                  target_cache=None, case_keys=None, max_workspace_bytes=1 << 30):
+                  target_cache=None, case_keys=None, max_workspace_bytes=1 << 30, surface=None):
     """[calculate_metrics(predictions (* body_masks), labels, threshold=t, spacing) for t in
     thresholds], key for key and bit for bit, from ONE pass per case: one l3u_thr_levels (the
     level encoding of all distinct float32 thresholds and the voxel histogram DSC needs), one
@@ -476,8 +476,18 @@ def sweep_metrics(predictions, labels, thresholds, spacing=(4.0, 4.0, 4.0), body
     number of native calls per case does not depend on the number of thresholds; when the K level
     workspaces exceed `max_workspace_bytes` the levels run in groups.  Cases are numpy arrays or
     device tensors.  Inputs the level kernels do not take (a [B, D, H, W] case with B > 1, more
-    than 32 distinct thresholds, dtypes numpy would promote differently) loop calculate_metrics."""
+    than 32 distinct thresholds, dtypes numpy would promote differently) loop calculate_metrics.
+
+    `surface` (default None: nothing changes) = {"tolerances_mm": [...], "percentile": 95.0} adds
+    the boundary metrics of light_unet/surface.py to every threshold's dict: hd95_mean and
+    assd_mean (means over the cases whose prediction and target surfaces are both non-empty, nan
+    when there are none), nsd_mean (one value per tolerance, the mean over the cases where not
+    both surfaces are empty) and surface_cases (the count the first two means ran over).  Cases
+    are [D, H, W] volumes then."""
     thresholds = [t for t in thresholds]
+    if surface is not None:
+        from . import surface as _surface
+        surf_tol, surf_q = _surface.check_config(surface)
     pred_list, label_list = _case_list(predictions, "predictions"), _case_list(labels, "labels")
     n_cases = len(pred_list)
     mask_list = [None] * n_cases if body_masks is None else _case_list(body_masks, "body_masks")
@@ -485,6 +495,23 @@ def sweep_metrics(predictions, labels, thresholds, spacing=(4.0, 4.0, 4.0), body
         raise ValueError("body_masks must hold one entry (or None) per case")
     if not thresholds:
         return []
+    out = _sweep(pred_list, label_list, mask_list, thresholds, spacing, target_cache, case_keys,
+                 max_workspace_bytes)
+    if surface is not None:
+        rows = [_surface.case_surface_metrics(_squeeze(_arr(p)), _squeeze(_arr(t)), thresholds, sp,
+                                              surf_tol, surf_q,
+                                              body_mask=None if m is None else _squeeze(_arr(m)))
+                for p, t, m, sp in zip(pred_list, label_list, mask_list,
+                                       _spacing_per_case(spacing, n_cases))]
+        for k, d in enumerate(out):
+            d.update(_surface.aggregate([r[k] for r in rows], len(surf_tol)))
+    return out
+
+
+def _sweep(pred_list, label_list, mask_list, thresholds, spacing, target_cache, case_keys,
+           max_workspace_bytes):
+    """sweep_metrics without the surface keys."""
+    n_cases = len(pred_list)
     preds = [_squeeze(_arr(p)) for p in pred_list]
     targets = [_squeeze(_arr(t)) for t in label_list]
     masks = [None if m is None else _squeeze(_arr(m)) for m in mask_list]
