@@ -1086,6 +1086,56 @@ int l3u_surf_nblocks(long long n);
 int l3u_surf_reduce(const double* dist, const unsigned long long* surf, const double* tol, int ntol,
                     double* sd, double* part, double* res, int D, int H, int W, hipStream_t stream);
 
+/* ---- lesion uptake (csrc/quantify.hip; light_unet/quantify.py) ----
+ * All volumes are [D][H][W] with D * H * W < 2^31 (else hipErrorInvalidValue before any launch);
+ * labels is l3u_ccl_label's int32 labelling (0 = background).  No float atomics anywhere: the same
+ * input gives the same bits.  Uptake must be finite.
+ *
+ * l3u_qt_peak: the spherical mean around every labelled voxel c,
+ *   peak[c] = S(c) / n(c),  S(c) = the double sum, from +0.0 and in table order, of
+ *   uptake[c + offs[i]] over the offsets that stay inside the volume, n(c) their count,
+ * the division in double.  offs: DEVICE int[noff][3] (dz, dy, dx), 1 <= noff <= 729, every
+ * |dz| <= rz, |dy| <= ry, |dx| <= rx, and rz, ry, rx in 0..4 (the halo a workgroup stages; offsets
+ * beyond it are clamped to it, never read outside the tile).  peak is written at labelled voxels
+ * only; a 4 x 8 x 64 tile without one costs the read of its labels.
+ *
+ * l3u_qt_reduce: per label the voxel count, the double sum of uptake, the maximum of uptake with
+ * the smallest flat index attaining it, and (peak != NULL) the same for peak.  items: DEVICE
+ * int[n_items][8] = (label, z0, z1, y0, y1, x0, x1, 0), half-open boxes that partition each label's
+ * voxels (clipped to the volume), the items of label l at first[l - 1] .. first[l] (DEVICE
+ * int[num + 1], ascending).  One workgroup per item reduces in a fixed order into part
+ * (n_items * 8 doubles of workspace); res[num][8] (double) = count, sum, max, its voxel, peak max,
+ * its voxel, 0, 0, the items merged in item order (voxel = INT_MAX and max = -inf for a label without
+ * voxels; the peak columns likewise when peak is NULL).
+ *
+ * l3u_qt_corners: out = the corner voxels of the packed mask `in` (l3u_pp_pack's format): mask
+ * voxels that have, on each of the three axes, at least one of their two neighbours outside the
+ * mask, the outside of the volume counting as outside.  Only they can be an end of the mask's
+ * farthest pair.  bcnt[b] = the corner voxels in words [256 b, 256 b + 256) for
+ * b < l3u_qt_corner_blocks(D, H, W) (0 for bad dimensions), bpre[b] = the sum of bcnt[0 .. b) and
+ * bpre[blocks] = their total.  in != out, bcnt != bpre.
+ * l3u_qt_compact: cand[k] = int[4] (z, y, x, flat index) of the k-th set voxel of `bits` in
+ * ascending flat index, from l3u_qt_corners' bpre; writes below ncand only.
+ *
+ * l3u_qt_farthest: over the 2 <= ncand <= 2^18 candidates, res[3] (double) =
+ *   the maximum over pairs of d2 = fl(fl(fl(dz sz)^2 + fl(dy sy)^2) + fl(dx sx)^2)
+ * (dz, dy, dx the integer coordinate differences; nothing fused), then the flat indices i < j of
+ * the pair attaining it with the smallest i, then the smallest j (cand ascending in flat index).
+ * part: l3u_qt_pair_parts(ncand) * 2 unsigned long long of workspace (0 outside 2..2^18). */
+int l3u_qt_peak(const float* uptake, const int* labels, const int* offs, int noff, int rz, int ry,
+                int rx, double* peak, int D, int H, int W, hipStream_t stream);
+int l3u_qt_reduce(const float* uptake, const int* labels, const double* peak, const int* items,
+                  int n_items, const int* first, int num, double* part, double* res, int D, int H,
+                  int W, hipStream_t stream);
+int l3u_qt_corner_blocks(int D, int H, int W);
+int l3u_qt_corners(const unsigned long long* in, unsigned long long* out, int* bcnt, int* bpre, int D,
+                   int H, int W, hipStream_t stream);
+int l3u_qt_compact(const unsigned long long* bits, const int* bpre, int* cand, int ncand, int D, int H,
+                   int W, hipStream_t stream);
+int l3u_qt_pair_parts(int ncand);
+int l3u_qt_farthest(const int* cand, int ncand, double sz, double sy, double sx,
+                    unsigned long long* part, double* res, hipStream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

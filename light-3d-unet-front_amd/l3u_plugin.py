@@ -53,6 +53,7 @@ def load():
     importlib.import_module(ALIAS + ".patches")
     importlib.import_module(ALIAS + ".preprocess")
     importlib.import_module(ALIAS + ".surface")
+    importlib.import_module(ALIAS + ".quantify")
     importlib.import_module(ALIAS + ".inference")
     return mod
 

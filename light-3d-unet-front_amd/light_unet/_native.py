@@ -152,6 +152,16 @@ _SIGS = {
     "l3u_surf_mask": [P, P, I, I, I, P],
     "l3u_surf_nblocks": [L],
     "l3u_surf_reduce": [P, P, P, I, P, P, P, I, I, I, P],
+    # lesion uptake: the sphere mean (uptake, labels, offs, noff, rz, ry, rx, peak, D, H, W), the
+    # per-lesion reductions over (label, slab) items, the corner voxels of a packed mask with
+    # their prefix counts, their coordinate list, and the farthest pair of that list
+    "l3u_qt_peak": [P, P, P, I, I, I, I, P, I, I, I, P],
+    "l3u_qt_reduce": [P, P, P, P, I, P, I, P, P, I, I, I, P],
+    "l3u_qt_corner_blocks": [I, I, I],
+    "l3u_qt_corners": [P, P, P, P, I, I, I, P],
+    "l3u_qt_compact": [P, P, P, I, I, I, I, P],
+    "l3u_qt_pair_parts": [I],
+    "l3u_qt_farthest": [P, I, D, D, D, P, P, P],
 }
 # entry points with a _bf16 twin (same arguments; saved activations stored as bf16, gradients
 # fp32, include/l3u.h)
@@ -176,7 +186,7 @@ _QUERIES = {"l3u_abi_version", "l3u_dw3_nchunk", "l3u_pw_stat_nsb", "l3u_pw_bwd_
             "l3u_ccl_nchunks", "l3u_dwpw_supported", "l3u_dwpw_stat_nsb",
             "l3u_dw3_bwd_rank1", "l3u_pw_bwd2_supported", "l3u_pw_bwd_chunk",
             "l3u_ccl_lv_max_levels", "l3u_pp_select_ws_bytes", "l3u_pp_morph_max_iters",
-            "l3u_loc_nblocks", "l3u_surf_nblocks"}
+            "l3u_loc_nblocks", "l3u_surf_nblocks", "l3u_qt_corner_blocks", "l3u_qt_pair_parts"}
 
 LOC_BLOCK = 4096    # L3U_LOC_BLOCK
 

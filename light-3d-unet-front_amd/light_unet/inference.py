@@ -10,12 +10,13 @@ to save.  Reading the NIfTI image / mask and writing the map and the JSON stay w
 import math
 
 from . import lesion
+from . import quantify as _quantify
 from . import resample
 from .utils import sliding_window_inference_3d
 
 
 def infer_volume(image, model, config, body_mask=None, spacing=(4.0, 4.0, 4.0), threshold=None,
-                 forward_cache=None, tta_flips=None, native_shape=None):
+                 forward_cache=None, tta_flips=None, native_shape=None, uptake=None, quantify=None):
     """(prob_map, bboxes) of one case: prob_map the float32 numpy [D, H, W] map the reference
     saves (times `body_mask` when config["data"]["body_mask"] has both `enabled` and
     `apply_to_inference`, inferencer.py:136-137, :161-162; otherwise the mask is ignored), bboxes
@@ -32,7 +33,22 @@ def infer_volume(image, model, config, body_mask=None, spacing=(4.0, 4.0, 4.0), 
     that [D, H, W] shape on the device (resample.resample_volume, order 1) and the boxes are
     extracted there, so prob_map and bbox_voxel are on the scanner's grid and `spacing` is the
     native one: the volume threshold converts through it, and the boxes grow by
-    ceil(data.bbox_expansion_mm / spacing[a]) voxels on axis a (at 4 mm the reference's 3)."""
+    ceil(data.bbox_expansion_mm / spacing[a]) voxels on axis a (at 4 mm the reference's 3).
+
+    `uptake` (default None: nothing changes, the result stays a 2-tuple) is the case's SUV volume
+    on the grid the map ends on (the native grid when `native_shape` is given), numpy or device:
+    the result is then (prob_map, bboxes, report) with report = quantify.lesion_uptake(uptake,
+    map, ...) on the device-resident map at the boxes' threshold, minimum voxel count and spacing,
+    so report["lesions"][i]["label"] == bboxes[i]["mask_id"].  `quantify` = {"peak_ml": ...,
+    "dmax": ...} sets its options (quantify.check_config)."""
+    if uptake is None and quantify is not None:
+        raise ValueError("quantify sets the options of the uptake report: pass uptake too")
+    if uptake is not None:
+        peak_ml, want_dmax = _quantify.check_config(quantify)
+        want = tuple(int(v) for v in (native_shape if native_shape is not None else image.shape[-3:]))
+        if tuple(int(v) for v in uptake.shape) != want:
+            raise ValueError(f"uptake must be on the grid the map ends on, {want}; got "
+                             f"{tuple(uptake.shape)}")
     data = config["data"]
     bm = config.get("data", {}).get("body_mask", {})
     apply_mask = bm.get("apply_to_inference", False) and bm.get("enabled", False)
@@ -52,4 +68,9 @@ def infer_volume(image, model, config, body_mask=None, spacing=(4.0, 4.0, 4.0), 
     bboxes = lesion.extract_bboxes(prob, threshold=threshold,
                                    min_volume_cc=data["volume_threshold"]["inference_cc"],
                                    spacing=spacing, expansion_voxels=expansion)
-    return prob.cpu().numpy(), bboxes   # the one download
+    if uptake is None:
+        return prob.cpu().numpy(), bboxes   # the one download
+    report = _quantify.lesion_uptake(
+        uptake, prob, spacing=spacing, threshold=threshold, peak_ml=peak_ml, dmax=want_dmax,
+        min_size=lesion.min_voxels_for(data["volume_threshold"]["inference_cc"], spacing))
+    return prob.cpu().numpy(), bboxes, report
