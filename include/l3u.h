@@ -1136,6 +1136,56 @@ int l3u_qt_pair_parts(int ncand);
 int l3u_qt_farthest(const int* cand, int ncand, double sz, double sy, double sx,
                     unsigned long long* part, double* res, hipStream_t stream);
 
+/* ---- resegmentation by an uptake threshold (csrc/resegment.hip; light_unet/resegment.py) ----
+ * Seeded region growing restricted to a box, one threshold per seed.  The seeds are the labels
+ * 1..n of `seeds` (l3u_ccl_label's int32 labelling of a [D][H][W] volume, D * H * W < 2^31, else
+ * hipErrorInvalidValue before any launch).  For seed i (label i + 1), with thr[i] a double:
+ *   cand_i(v)  = (double)uptake[v] >= thr[i]  and, with a body mask, body[v] != 0
+ *                (body_dtype 0 float, 2 uint8: l3u_pp_pack's codes; body may be NULL);
+ *   box_i      = the half-open box of items[i], inside the volume;
+ *   R_i        = the voxels v of box_i with cand_i(v) joined to a voxel of seed i with cand_i by a
+ *                6-neighbour path whose voxels all lie in box_i and satisfy cand_i (connectivity
+ *                through voxels outside the box does not count); with grow == 0 only the seed's
+ *                own voxels with cand_i;
+ *   own[v]     = max over {i : v in R_i} of (n - i), by integer atomicMax on a map the caller has
+ *                ZEROED: n + 1 - own[v] is the smallest label reaching v, 0 stays "none";
+ *   reached[i] += |R_i|  (the caller zeroes it).
+ * Uptake must be finite.  All integer and bit work but that one comparison: the same input gives
+ * the same bits; no float atomics.
+ *
+ * items: DEVICE int[n][8] = (label = i + 1, z0, z1, y0, y1, x0, x1, path), path =
+ * l3u_rs_path(z1 - z0, y1 - y0, x1 - x0, max_lds_bytes): 0 when the box's two bitmaps (candidates
+ * and reached: 64-bit words, x fastest from x0, rows padded to whole words, as l3u_pp_pack packs a
+ * volume) and a 16-byte header fit max_lds_bytes of LDS (0: the default, 64 KiB, which is also the
+ * most; 16 at least), 1 when they do not, -1 for bad arguments.  A row that is not consistent
+ * (box outside the volume, another path than the budget allows) is skipped, never run.
+ *
+ * l3u_rs_grow: path 0 seeds are built, grown to the fixed point (sweeps of
+ * reached |= cand & neighbours(reached) until one changes no word; sweeps[i] = the sweeps that
+ * changed one) and committed to own / reached by one workgroup each.  For path 1 seeds it builds
+ * the bitmaps in `arena`: seed i holds 3 nw_i words from aoff[i] (DEVICE long long[n]; nw_i = rows
+ * x words per row): candidates, then two reached buffers, the seed in the first.  tiles: DEVICE
+ * int[n_tiles][4] = (i, z, y, word) origins, relative to the box, of the 8 x 8 x 4-word tiles that
+ * partition the path 1 boxes (l3u_rs_tiles(nz, ny, nx) of them per box); n_tiles may be 0.
+ * l3u_rs_sweep: one launch grows every tile, staged with a halo of one plane, row and word, to its
+ * own fixed point from reached buffer 1 + flip (flip 0 or 1) into buffer 2 - flip, and adds the
+ * number of interior words it changed to *counter (DEVICE): relaunch with flip alternating until a
+ * launch adds 0.
+ * l3u_rs_commit: reached buffer 1 + flip of the path 1 seeds into own / reached. */
+int l3u_rs_path(int nz, int ny, int nx, int max_lds_bytes);
+int l3u_rs_tiles(int nz, int ny, int nx);
+int l3u_rs_grow(const float* uptake, const int* seeds, const void* body, int body_dtype,
+                const int* items, const double* thr, int n, int grow, int* own,
+                unsigned long long* reached, int* sweeps, const int* tiles, int n_tiles,
+                const long long* aoff, unsigned long long* arena, int max_lds_bytes, int D, int H,
+                int W, hipStream_t stream);
+int l3u_rs_sweep(const int* items, int n, const int* tiles, int n_tiles, const long long* aoff,
+                 unsigned long long* arena, int flip, unsigned int* counter, int D, int H, int W,
+                 hipStream_t stream);
+int l3u_rs_commit(const int* items, int n, const int* tiles, int n_tiles, const long long* aoff,
+                  const unsigned long long* arena, int flip, int* own, unsigned long long* reached,
+                  int D, int H, int W, hipStream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

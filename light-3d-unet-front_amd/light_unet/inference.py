@@ -12,11 +12,13 @@ import math
 from . import lesion
 from . import quantify as _quantify
 from . import resample
+from . import resegment as _resegment
 from .utils import sliding_window_inference_3d
 
 
 def infer_volume(image, model, config, body_mask=None, spacing=(4.0, 4.0, 4.0), threshold=None,
-                 forward_cache=None, tta_flips=None, native_shape=None, uptake=None, quantify=None):
+                 forward_cache=None, tta_flips=None, native_shape=None, uptake=None, quantify=None,
+                 resegment=None):
     """(prob_map, bboxes) of one case: prob_map the float32 numpy [D, H, W] map the reference
     saves (times `body_mask` when config["data"]["body_mask"] has both `enabled` and
     `apply_to_inference`, inferencer.py:136-137, :161-162; otherwise the mask is ignored), bboxes
@@ -40,11 +42,18 @@ def infer_volume(image, model, config, body_mask=None, spacing=(4.0, 4.0, 4.0), 
     the result is then (prob_map, bboxes, report) with report = quantify.lesion_uptake(uptake,
     map, ...) on the device-resident map at the boxes' threshold, minimum voxel count and spacing,
     so report["lesions"][i]["label"] == bboxes[i]["mask_id"].  `quantify` = {"peak_ml": ...,
-    "dmax": ...} sets its options (quantify.check_config)."""
+    "dmax": ...} sets its options (quantify.check_config).  `resegment` = {"method": ..., "value":
+    ..., "grow_mm": ...} (resegment.check_resegment; default None: nothing changes) has the report
+    measure the lesions as resegment.resegment_lesions redraws them on the uptake: the boxes stay
+    those of the network's map, and report["lesions"][k]["seed_label"] is the mask_id of the box
+    the region grew from."""
     if uptake is None and quantify is not None:
         raise ValueError("quantify sets the options of the uptake report: pass uptake too")
+    if uptake is None and resegment is not None:
+        raise ValueError("resegment redraws the lesions on the uptake: pass uptake too")
     if uptake is not None:
         peak_ml, want_dmax = _quantify.check_config(quantify)
+        _resegment.check_resegment(resegment)
         want = tuple(int(v) for v in (native_shape if native_shape is not None else image.shape[-3:]))
         if tuple(int(v) for v in uptake.shape) != want:
             raise ValueError(f"uptake must be on the grid the map ends on, {want}; got "
@@ -72,5 +81,6 @@ def infer_volume(image, model, config, body_mask=None, spacing=(4.0, 4.0, 4.0), 
         return prob.cpu().numpy(), bboxes   # the one download
     report = _quantify.lesion_uptake(
         uptake, prob, spacing=spacing, threshold=threshold, peak_ml=peak_ml, dmax=want_dmax,
-        min_size=lesion.min_voxels_for(data["volume_threshold"]["inference_cc"], spacing))
+        min_size=lesion.min_voxels_for(data["volume_threshold"]["inference_cc"], spacing),
+        resegment=resegment)
     return prob.cpu().numpy(), bboxes, report

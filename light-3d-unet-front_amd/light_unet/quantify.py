@@ -204,7 +204,7 @@ def _zyx(flat, shape):
 
 # ------------------------------------------------------------------ the public entry point
 def lesion_uptake(uptake, mask, spacing=(4.0, 4.0, 4.0), threshold=0.5, min_size=0, peak_ml=1.0,
-                  dmax=True):
+                  dmax=True, resegment=None):
     """The uptake report of one case.
 
     uptake: [D, H, W] volume (SUV, or whatever unit the caller holds), numpy or device tensor, taken
@@ -220,9 +220,20 @@ def lesion_uptake(uptake, mask, spacing=(4.0, 4.0, 4.0), threshold=0.5, min_size
     as the module docstring defines them.  Without a lesion the list is empty and the maxima are
     0.0; with fewer than two mask voxels dmax_mm is 0.0 and dmax_voxels None; dmax_centroid_mm is
     the largest distance between two centroids (0.0 with fewer than two lesions).  peak_ml=None
-    leaves the suv_peak keys out, dmax=False the dmax_mm and dmax_voxels keys."""
+    leaves the suv_peak keys out, dmax=False the dmax_mm and dmax_voxels keys.
+
+    resegment (default None: nothing changes) = {"method": "fixed" or "relative", "value": ...,
+    "grow_mm": ... or None} (resegment.check_resegment) measures the lesions as
+    resegment.resegment_lesions redraws them on the uptake, seeded by the lesions above: the report
+    is that of its regions, every lesion row gains "seed_label", "seed_voxels" and "threshold", and
+    the report "resegment": {"method", "value", "grow_mm", "below_threshold", "absorbed"}, the two
+    lists holding the labels of the seeds that left no region."""
     sp = _spacing3(spacing)
     peak_ml = _peak_ml(peak_ml)
+    rs_cfg = None
+    if resegment is not None:
+        from . import resegment as _rs
+        rs_cfg = _rs.check_resegment(resegment)
     up_t = uptake if isinstance(uptake, torch.Tensor) else torch.from_numpy(
         np.ascontiguousarray(np.asarray(uptake)))
     shape = _shape_of(up_t, "uptake")
@@ -241,6 +252,10 @@ def lesion_uptake(uptake, mask, spacing=(4.0, 4.0, 4.0), threshold=0.5, min_size
     dev = mask.labels.device if given else _device()
     up = lesion._volume(up_t, dev)
     comp = mask if given else lesion.label(mask, threshold, min_size)
+    rs = None
+    if rs_cfg is not None:
+        rs = _rs.resegment_lesions(up, comp, sp, method=rs_cfg[0], value=rs_cfg[1], grow_mm=rs_cfg[2])
+        comp = rs.components
     voxel_ml = sp[0] * sp[1] * sp[2] / 1000.0
     sp_arr = np.asarray(sp, dtype=np.float64)
     lesions = []
@@ -264,6 +279,11 @@ def lesion_uptake(uptake, mask, spacing=(4.0, 4.0, 4.0), threshold=0.5, min_size
                 row["suv_peak_voxel"] = _zyx(res[i, 5], shape)
             row["tlg"] = suv_mean * volume_ml
             row["centroid_mm"] = [float(v) for v in centers[i]]
+            if rs is not None:
+                seed = int(rs.seed_label[i])
+                row["seed_label"] = seed
+                row["seed_voxels"] = int(rs.seed_voxels[seed - 1])
+                row["threshold"] = float(rs.thresholds[seed - 1])
             lesions.append(row)
     total = sum(r["voxels"] for r in lesions)
     out = {"lesions": lesions, "n_lesions": len(lesions),
@@ -276,6 +296,10 @@ def lesion_uptake(uptake, mask, spacing=(4.0, 4.0, 4.0), threshold=0.5, min_size
         out["dmax_mm"], out["dmax_voxels"] = (_dmax(comp.labels.contiguous(), shape, sp)
                                               if total >= 2 else (0.0, None))
     out["dmax_centroid_mm"] = centroid_dmax([r["centroid_mm"] for r in lesions])
+    if rs is not None:
+        out["resegment"] = {"method": rs_cfg[0], "value": rs_cfg[1], "grow_mm": rs_cfg[2],
+                            "below_threshold": [int(i) + 1 for i in np.flatnonzero(rs.status == 1)],
+                            "absorbed": [int(i) + 1 for i in np.flatnonzero(rs.status == 2)]}
     return out
 
 
