@@ -6,7 +6,8 @@ library's host queries and order C-ABI calls.  Every call and every engine alloc
 consecutive steps is written as one text line, with pointers replaced by `buffer+byteoffset`, so
 the text depends on the schedule alone.  tests/golden/launch_trace.json keeps one sha256 per case;
 tests/test_launch_trace.py compares them, so a change of engine.py that alters any launch, argument,
-buffer layout or reduction item shows up as a changed hash.
+buffer layout or reduction item shows up as a changed hash.  tests/test_footprints.py reads the
+same steps' raw events and buffers (trace_raw) to hold every call against the footprint table.
 
 usage: python tools/launch_trace.py            compare every case with the golden file
        python tools/launch_trace.py --dump CASE   print one case's text (diff two checkouts)
@@ -209,8 +210,10 @@ class Canon:
         return f"{ev[1]}({', '.join(self.arg(a) for a in ev[2])})"
 
 
-def trace(case):
-    """(canonical text, number of calls, names called) of one case."""
+def trace_raw(case):
+    """(events, labelled buffers, trailing text lines) of one case: the Recorder's raw events with
+    their live pointer arguments, and every tensor those pointers fall in by its label (the
+    case's buffers, the engine's allocations a0.., the arenas and the item table)."""
     saved = {sw: getattr(E, sw) for sw in case.off}
     for sw in case.off:
         setattr(E, sw, False)
@@ -245,10 +248,16 @@ def trace(case):
         tail += ["item " + " ".join(str(v) for v in row) for row in items.tolist()]
         tail.append(f"cover_once {engine._cover_once[key]}")
     tail.append(f"applied_update {engine.applied_update}")
-    canon = Canon(labelled)
-    lines = [canon.event(ev) for ev in rec.events] + tail
-    names = [ev[1] for ev in rec.events if ev[0] == "call"]
     case.buf = case.optim = None
+    return rec.events, labelled, tail
+
+
+def trace(case):
+    """(canonical text, number of calls, names called) of one case."""
+    events, labelled, tail = trace_raw(case)
+    canon = Canon(labelled)
+    lines = [canon.event(ev) for ev in events] + tail
+    names = [ev[1] for ev in events if ev[0] == "call"]
     return "\n".join(lines) + "\n", len(names), set(names)
 
 
