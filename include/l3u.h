@@ -684,7 +684,9 @@ int l3u_gconv3_bwd_weight(const float* dy, long long dy_nstride, const float* x,
  * lr and step live on the device (graph-replay safe).  ONE launch: the last workgroup
  * to finish (ticket order; *ticket starts at 0 and is reset) advances *step and, when
  * counter2 != NULL, *counter2 (the model's Dropout3d stream counter, unet3d.py:66, so a
- * captured training step needs no separate counter launches)                                   */
+ * captured training step needs no separate counter launches).  p, g, m and v select the path
+ * together: when all four are 16-byte aligned the update runs on 16-byte loads and stores (the
+ * last numel % 4 elements one by one), otherwise element by element; both give the same bits.  */
 int l3u_adamw_tick(float* p, const float* g, float* m, float* v, long long numel, const float* lr,
                    float beta1, float beta2, float eps, float weight_decay, int* step,
                    float grad_scale, int* ticket, int* counter2, hipStream_t stream);
@@ -693,6 +695,8 @@ int l3u_adamw_tick(float* p, const float* g, float* m, float* v, long long numel
  * items[nitems][8] int64 = {src_off, count, istride, tstride, len<=256, dst_off, accumulate, f64}:
  * dst[dst_off+t] (+)= sum_{i<count} src[src_off + i*istride + t*tstride], summed in fp64;
  * f64 != 0: the source is fp64 and offsets/strides count doubles from the same base.
+ * Each output is ONE fp32 rounding of an fp64 sum taken in a fixed order (a function of the
+ * item alone), and accumulate != 0 adds the prior dst in fp64 before that rounding.
  * src is 16-byte aligned (checked), and every item's per-lane offsets fit 32 bits:
  * (count-1)*istride + (len-1)*tstride < 2^31 (the engine checks it when it records an item). */
 int l3u_reduce_segments(const float* src, const long long* items, int nitems, float* dst,

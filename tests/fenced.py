@@ -34,6 +34,7 @@ import bisect
 import contextlib
 import ctypes
 
+import numpy as np
 import torch
 
 import footprints as fp
@@ -41,6 +42,7 @@ from light_unet import _native as nat
 
 GUARD = 4096
 POISON = 0x7FC5A5A5      # a quiet NaN with a payload; compared as an integer
+MASK_LOOP_MAX = 256      # _mask: more runs than this are marked in one pass on the host
 
 
 class FenceError(AssertionError):
@@ -79,6 +81,16 @@ def _active_blocks():
 
 
 def _mask(n, ivs, dev):
+    if len(ivs) > MASK_LOOP_MAX:
+        # many short runs (the strided footprint of a reduction item): one pass on the host
+        # instead of one fill per run; the same mask as the loop below for any list of runs
+        # (overlapping, touching, clipped at either end; an empty or inverted run covers nothing)
+        b = np.clip(np.asarray(ivs, dtype=np.int64).reshape(-1, 2), 0, n)
+        b = b[b[:, 0] < b[:, 1]]
+        d = np.zeros(n + 1, dtype=np.int32)
+        np.add.at(d, b[:, 0], 1)
+        np.add.at(d, b[:, 1], -1)
+        return torch.from_numpy(np.cumsum(d[:-1]) > 0).to(dev)
     m = torch.zeros(n, dtype=torch.bool, device=dev)
     for lo, hi in ivs:
         m[max(lo, 0):max(hi, 0)] = True

@@ -8,11 +8,14 @@ chunk, partial tiles, strided concat halves, rank-1 operands, 4-byte-aligned sto
 added to them.
 
 Re-exported: every test of test_ops_gpu and test_dwpw_gpu, those of test_tail_bwd_gpu but one; the
-kernel tests of test_gconv_gpu (test_gconv3_*), the twin tests and test_casts of test_bf16_gpu, and the
-stand-alone and out_conv kernel tests of test_loss_family_gpu.
+kernel tests of test_gconv_gpu (test_gconv3_*), the twin tests and test_casts of test_bf16_gpu, the
+stand-alone and out_conv kernel tests of test_loss_family_gpu, and those of test_step_tail_gpu but
+two (the 3000-item launch and the 2601-item ticket cases included: 0.4 s and 0.7 s fenced).
 
 Left out (they reach the library under graph capture, through a whole model / TrainStep whose
 launches the engine-level tests below and tests/test_footprints.py cover, or in a subprocess):
+  test_step_tail_gpu: test_adamw_graph_replay_equals_eager (graph),
+    test_reduce_refuses_misaligned_src (it launches through _native.query to read the error code)
   test_tail_bwd_gpu: test_tail_pair_rejects_dscale_with_dpool (it launches through
     _native.query to read the error code, which the fence does not replace)
   test_gconv_gpu: test_variant_model_matches_reference_golden,
@@ -36,7 +39,9 @@ data-path kernels are not reached from here).
 The harness tests itself on four fake entry points written with plain torch ops on the shadow
 pointers: a well-behaved one passes, a store one element past the output, a load from before the
 input that reaches the result, and a store into a read-only operand are each reported with their
-argument and offset.
+argument and offset.  The same on a written footprint of 600 one-element runs (the one-pass mask
+of fenced.py, which tests/test_footprints.py holds equal to the run-by-run loop on the CPU): a
+store into a gap between the runs and a gap's value carried into an output are reported.
 
 The engine-level test (not fenced, eager): one forward + loss + backward, then the same step again
 with both arenas and every buffer the engine allocates filled with NaN first; output, loss and the
@@ -49,6 +54,10 @@ slowest case 1.1 s, test_dw3_bwd at 4 x 16 x 48^3), the same 468 cases unfenced 
 modules 23.0 s.  No violation was found in any of them, nor by the engine-level test.  With the
 tail bound of csrc/misc.hip cast_kernel moved by one (`t < n + 1`, a scratch build): the plain
 test_bf16_gpu.test_casts passes, the fenced one fails (l3u_cast_bf16_f32 argument 1, byte +4004).
+2026-10-21, with test_step_tail_gpu's 233 cases added (strided reduction items have a footprint of
+up to 240 000 one-element runs; fenced.py masks more than 256 runs in one pass on the host): the
+701 re-exported cases fenced 34.3 s (1990 fenced calls, 13.7 GiB shadowed), of which the 233 new
+ones 12.9 s (476 calls, 1.0 GiB; slowest 0.73 s) against 5.2 s unfenced in their own module.
 """
 import pytest
 import torch
@@ -78,6 +87,14 @@ from test_ops_gpu import (test_adamw_tick_matches_torch, test_box_copy_pad_and_c
                           test_pw_bwd_fused, test_pw_bwd_k1_rank1_y, test_pw_bwd_matches_unfused,
                           test_pw_bwd_tail_equals_apply_then_pw_bwd, test_pw_bwd_weight,
                           test_pw_fwd, test_pw_fwd2_equals_two_pw_fwd, test_reduce_segments)
+from test_step_tail_gpu import (test_adamw_five_steps, test_adamw_lr_rewritten_on_the_device,  # noqa: F401
+                                test_adamw_one_step, test_adamw_options,
+                                test_adamw_scalar_path_equals_float4_path, test_counter_add,
+                                test_fused_equals_two_launches, test_fused_tickets,
+                                test_fused_tickets_many_items, test_reduce_3000_mixed_items, test_reduce_engine_items,
+                                test_reduce_hand_lists,
+                                test_reduce_near_misses_equal_the_float4_item,
+                                test_reduce_order_of_additions)
 from test_tail_bwd_gpu import (test_outconv_dz_forms, test_tail_bwd_column_splits,  # noqa: F401
                                test_tail_bwd_rank1_yr_vs_fp64, test_tail_bwd_strided_views,
                                test_tail_bwd_vs_fp64)
@@ -186,6 +203,58 @@ def test_fence_reports_planted_violations(cuda, fakes, n, lead):
     # the caller's input is untouched by the refused calls (they ran on the shadow)
     assert torch.equal(x.cpu() * 2, ref)
     assert nat.call is not None and not isinstance(nat.call, fenced.Fence)
+
+
+def _strided_good(src, dst, n, stream):
+    _f32_at(dst, 2 * n)[0::2].copy_(2 * _f32_at(src, n))
+
+
+def _strided_writes_gap(src, dst, n, stream):
+    _strided_good(src, dst, n, stream)
+    _f32_at(dst + 4 * (2 * 301 + 1), 1).fill_(1.0)           # the gap after output 301
+
+
+def _strided_reads_gap(src, dst, n, stream):
+    _strided_good(src, dst, n, stream)
+    _f32_at(dst + 8 * 7, 1).add_(_f32_at(dst + 8 * 300 + 4, 1))   # a gap's value into output 7
+
+
+def test_fence_reports_violations_in_a_strided_footprint(cuda, monkeypatch):
+    """A written footprint of 600 one-element runs, more than fenced.MASK_LOOP_MAX, so the mask
+    comes from the one-pass form that every fenced reduction item with a strided footprint gets:
+    the gaps between the runs are poisoned and watched like everything else outside."""
+    from light_unet import _native as nat
+    n = 600
+    assert n > fenced.MASK_LOOP_MAX
+    strided = {"l3u_fake_strided_good": _strided_good,
+               "l3u_fake_strided_writes_gap": _strided_writes_gap,
+               "l3u_fake_strided_reads_gap": _strided_reads_gap}
+    entry = ("src dst n", lambda a, E: {"src": ("r", fp.B(4 * a.n)),
+                                        "dst": ("w", [(8 * i, 8 * i + 4) for i in range(a.n)])}, ())
+    for name in strided:
+        monkeypatch.setitem(nat._SIGS, name, [nat.P, nat.P, nat.L, nat.P])
+        monkeypatch.setitem(fp.TABLE, name, entry)
+    x = torch.randn(n, generator=torch.Generator().manual_seed(5)).to(cuda)
+
+    def run(name):
+        y = torch.full((2 * n,), -3.0, device=cuda)
+        with fenced.fence(call=lambda nm, *a: strided[nm](*a)) as f:
+            nat.call(name, x.data_ptr(), y.data_ptr(), n, 0)
+        assert f.calls == 1 and f.tabled == 1 and not f.unmapped
+        return y
+
+    y = run("l3u_fake_strided_good")
+    # the runs come back, the caller's gaps are as they were
+    assert torch.equal(y[0::2], 2 * x) and bool((y[1::2] == -3.0).all())
+    with pytest.raises(fenced.FenceError) as e:
+        run("l3u_fake_strided_writes_gap")
+    assert (e.value.entry, e.value.arg, e.value.offset) == \
+        ("l3u_fake_strided_writes_gap", 1, 4 * (2 * 301 + 1))
+    assert "write outside" in e.value.kind
+    with pytest.raises(fenced.FenceError) as e:
+        run("l3u_fake_strided_reads_gap")
+    assert (e.value.entry, e.value.arg, e.value.offset) == ("l3u_fake_strided_reads_gap", 1, 8 * 7)
+    assert "poison value was read" in e.value.kind
 
 
 def test_fence_without_a_table_entry_guards_the_ends(cuda, fakes, monkeypatch):

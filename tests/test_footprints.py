@@ -28,7 +28,7 @@ from light_unet import _native as nat
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 ARENAS = ("fwd_arena", "bwd_arena")
 FENCED_SOURCES = ("test_ops_gpu", "test_tail_bwd_gpu", "test_dwpw_gpu", "test_gconv_gpu",
-                  "test_bf16_gpu", "test_loss_family_gpu")
+                  "test_bf16_gpu", "test_loss_family_gpu", "test_step_tail_gpu")
 
 
 @pytest.fixture(scope="module")
@@ -213,6 +213,49 @@ def test_table_conventions():
     dst = sorted((o.role, o.ivs) for o in ops if o.arg == 3)
     assert dst == [("rw", [(40, 48)]), ("w", [(0, 16)])]
     assert fp.footprints("l3u_ccl_label", (0,) * 10) is None
+
+
+def test_fence_mask_paths_agree(monkeypatch):
+    """tests/fenced.py _mask decides where the poison goes.  Its one-pass form (more than
+    MASK_LOOP_MAX runs: the strided footprints of reduction items) and its run-by-run loop give the
+    same mask, which is also a plain numpy restatement's: on random run lists (overlapping,
+    touching, empty, inverted, leaving the block at either end) and on the merged ascending runs
+    of a strided reduction item."""
+    import torch
+
+    import fenced
+    dev = torch.device("cpu")
+    rng = np.random.default_rng(11)
+
+    def both(n, ivs):
+        want = np.zeros(n, dtype=bool)
+        for lo, hi in ivs:
+            want[max(lo, 0):max(hi, 0)] = True
+        monkeypatch.setattr(fenced, "MASK_LOOP_MAX", 10 ** 9)
+        loop = fenced._mask(n, ivs, dev).numpy()
+        monkeypatch.setattr(fenced, "MASK_LOOP_MAX", -1)
+        fast = fenced._mask(n, ivs, dev).numpy()
+        assert loop.dtype == fast.dtype == np.bool_ and loop.shape == fast.shape == (n,)
+        assert np.array_equal(loop, want) and np.array_equal(fast, want)
+        return want
+
+    for _ in range(60):
+        n = int(rng.integers(1, 4000))
+        k = int(rng.integers(0, 600))
+        lo = rng.integers(-60, n + 60, k)
+        ivs = [(int(a), int(a + b)) for a, b in zip(lo, rng.integers(-6, 48, k))]
+        both(n, ivs)
+    assert both(16, [(12, 4), (2, 9)]).tolist() == [False] * 2 + [True] * 7 + [False] * 7
+    assert not both(16, [(-9, -2), (16, 40), (5, 5)]).any() and both(8, [(-3, 99)]).all()
+    # a strided fp64 column and fp32 rows, as the table hands them over (more runs than the
+    # threshold the fence uses: the one-pass form is what a fenced reduction call gets)
+    monkeypatch.undo()
+    rows = [[3, 700, 2, 1400, 3, 0, 0, 1], [9000, 300, 8, 1, 4, 40, 0, 0]]
+    ops = fp.footprints("l3u_reduce_segments", (1 << 40, 1 << 41, 2, 1 << 42, 0), lambda p, n: rows)
+    ivs = [o for o in ops if o.arg == 0][0].ivs
+    assert len(ivs) > fenced.MASK_LOOP_MAX
+    m = both(46000, ivs)
+    assert m.sum() == 700 * 3 * 8 + 300 * 4 * 4 and m[24] and not m[23] and not m[32]
 
 
 def test_fenced_modules_name_only_known_entry_points():
