@@ -42,7 +42,8 @@ typedef unsigned short l3u_bf16;   /* bfloat16 bit pattern (torch.bfloat16 stora
  * another.  3: l3u_norm_src.rank1, L3U_ADAMW_TICKET_INTS tickets, the l3u_sblock_* entry points
  * removed (round 3); the round-4 entry points.  5: l3u_pw_bwd_chunk (round 6).  Added since
  * without a new version (additive, nothing existing changed): l3u_window_occupancy,
- * l3u_window_blend_masked, l3u_window_gather_flip, l3u_window_tta_merge, l3u_resample. */
+ * l3u_window_blend_masked, l3u_window_gather_flip, l3u_window_tta_merge, l3u_resample,
+ * l3u_spline_prefilter, l3u_spline_prefilter_passes, l3u_resample_spline. */
 #define L3U_ABI_VERSION 5
 int l3u_abi_version(void);
 
@@ -1055,6 +1056,55 @@ int l3u_loc_select(const void* label, int label_dtype, const unsigned char* body
 int l3u_resample(const void* src, int src_dtype, int D, int H, int W, void* dst, int dst_dtype,
                  int oD, int oH, int oW, int order, const int* lo, const int* hi, const double* t,
                  hipStream_t stream);
+
+/* ---- cubic B-spline resampling (csrc/spline.hip; light_unet/resample.py: resample_spline) ----
+ * Order 3 of scipy.ndimage.zoom(src, zoom, order = 3, mode = "nearest", grid_mode = True), by this
+ * definition (the project's own, not a transcription of scipy's C code: its float32 results equal
+ * scipy 1.15.3's on tests/golden/spline.npz, the raw float64 sums agree to a few 1e-14 max|src|):
+ *  1. Padding.  NP = 12.  The padded volume p[D + 24][H + 24][W + 24] is
+ *     p[i0][i1][i2] = (double)src[clamp(i0 - 12)][clamp(i1 - 12)][clamp(i2 - 12)], each index
+ *     clamped to its axis: np.pad(src, 12, mode = "edge").
+ *  2. Prefilter.  Along axis 0, then axis 1, then axis 2, every line c[0 .. n-1] of the padded
+ *     volume is filtered in place in float64, every product, sum and difference rounded on its own
+ *     (no fused multiply-add, no reassociation, no scan), with the constants the caller computes
+ *     once in double arithmetic and passes in: z = sqrt(3.0) - 2.0, lam = (1.0 - z) * (1.0 - 1.0 / z),
+ *     k0 = 1.0 / (1.0 - z), kn = z / (z - 1.0):
+ *         c[i] = c[i] * lam                  for all i
+ *         c[0] = c[0] * k0
+ *         c[i] = c[i] + z * c[i-1]           i = 1 .. n-1
+ *         c[n-1] = kn * c[n-1]
+ *         c[i] = z * (c[i+1] - c[i])         i = n-2 .. 0
+ *     (the causal start is the closed form for a line extended by its first value; it differs from
+ *     scipy's start only inside the outer pad, which no tap reads: the smallest tap index is 10).
+ *  3. Tables.  Per axis with n_in source and n_out output samples and per output index o, in
+ *     float64: cc = (o + 0.5) * (n_in / n_out) - 0.5, f = floor(cc), y = cc - f, u = 1.0 - y,
+ *     start = (int)f - 1 + 12 (in [0, n_in + 20]), w0 = u*u*u/6.0, w1 = (y*y*(y-2.0)*3.0+4.0)/6.0,
+ *     w2 = (u*u*(u-2.0)*3.0+4.0)/6.0, w3 = 1.0 - w0 - w1 - w2.  Device tables of oD + oH + oW
+ *     entries, axis 0 first: start (int) and w (double [..][4]).
+ *  4. Interpolation.  dst[o0][o1][o2] = (float) of the float64 sum, started at 0.0 and accumulated
+ *     term by term over a, b, c in 0..3 in C order (a slowest), of
+ *     ((coef[s0 + a][s1 + b][s2 + c] * w_axis0[a]) * w_axis1[b]) * w_axis2[c]; with use_clip != 0
+ *     the float result becomes min(max(v, clip_lo), clip_hi) (a spline overshoots: a probability
+ *     map can leave [0, 1]).
+ * l3u_spline_prefilter: steps 1 and 2, src (src_dtype 0 float or 1 double) -> coef, a double
+ * buffer of (D + 24) * (H + 24) * (W + 24) elements (0.9 GB for a 400 x 400 x 600 case); the
+ * axis-0 pass reads src through the clamped indices, the other two run in place.  One prefilter
+ * serves any number of output grids.  l3u_spline_prefilter_passes runs a subset (bit 0: the axis-0
+ * pass src -> coef, bit 1: axis 1, bit 2: axis 2, on whatever coef holds; 7 is the prefilter), for
+ * timing the passes apart.
+ * l3u_resample_spline: step 4, coef of a [D][H][W] source -> dst[oD][oH][oW]; a start entry outside
+ * [0, n_in + 20] is clamped again on load: nothing outside coef is read.
+ * Every line's recursion and every output's sum runs in one thread in the stated order: no
+ * atomics, and the result does not depend on the launch shape.  NULL or aliased pointers, another
+ * src_dtype and sizes <= 0 return hipErrorInvalidValue before any launch. */
+int l3u_spline_prefilter(const void* src, int src_dtype, int D, int H, int W, double* coef,
+                         double z, double lam, double k0, double kn, hipStream_t stream);
+int l3u_spline_prefilter_passes(const void* src, int src_dtype, int D, int H, int W, double* coef,
+                                double z, double lam, double k0, double kn, int passes,
+                                hipStream_t stream);
+int l3u_resample_spline(const double* coef, int D, int H, int W, float* dst, int oD, int oH, int oW,
+                        const int* start, const double* w, float clip_lo, float clip_hi,
+                        int use_clip, hipStream_t stream);
 
 /* ---- surface-distance metrics (csrc/surface.hip; light_unet/surface.py) ----
  * l3u_edt: the exact Euclidean distance transform of a packed feature mask (l3u_pp_pack's format,

@@ -146,6 +146,12 @@ _SIGS = {
     "l3u_loc_select": [P, I, P, I, I, I, P, I, P, I, I, P, P],
     # resampling to another grid: (src, dtype, D, H, W, dst, dtype, oD, oH, oW, order, lo, hi, t)
     "l3u_resample": [P, I, I, I, I, P, I, I, I, I, I, P, P, P, P],
+    # cubic B-spline resampling: the prefilter (src, dtype, D, H, W, coef, z, lam, k0, kn), the
+    # same with a mask of the axis passes to run, and the gather (coef, D, H, W, dst, oD, oH, oW,
+    # start, w, clip_lo, clip_hi, use_clip)
+    "l3u_spline_prefilter": [P, I, I, I, I, P, D, D, D, D, P],
+    "l3u_spline_prefilter_passes": [P, I, I, I, I, P, D, D, D, D, I, P],
+    "l3u_resample_spline": [P, I, I, I, P, I, I, I, P, P, F, F, I, P],
     # surface distances: exact EDT of a packed mask (feat, sz, sy, sx, out, tmp, D, H, W, passes),
     # the surface of a packed mask, and the reductions over surface voxels (tol[ntol] on the HOST)
     "l3u_edt": [P, D, D, D, P, P, I, I, I, I, P],

@@ -18,7 +18,7 @@ from .utils import sliding_window_inference_3d
 
 def infer_volume(image, model, config, body_mask=None, spacing=(4.0, 4.0, 4.0), threshold=None,
                  forward_cache=None, tta_flips=None, native_shape=None, uptake=None, quantify=None,
-                 resegment=None):
+                 resegment=None, resample_order=1):
     """(prob_map, bboxes) of one case: prob_map the float32 numpy [D, H, W] map the reference
     saves (times `body_mask` when config["data"]["body_mask"] has both `enabled` and
     `apply_to_inference`, inferencer.py:136-137, :161-162; otherwise the mask is ignored), bboxes
@@ -36,6 +36,8 @@ def infer_volume(image, model, config, body_mask=None, spacing=(4.0, 4.0, 4.0), 
     extracted there, so prob_map and bbox_voxel are on the scanner's grid and `spacing` is the
     native one: the volume threshold converts through it, and the boxes grow by
     ceil(data.bbox_expansion_mm / spacing[a]) voxels on axis a (at 4 mm the reference's 3).
+    `resample_order` = 3 maps the map back by cubic B-spline interpolation instead
+    (resample.resample_spline with clip=(0.0, 1.0): a spline overshoots, a probability does not).
 
     `uptake` (default None: nothing changes, the result stays a 2-tuple) is the case's SUV volume
     on the grid the map ends on (the native grid when `native_shape` is given), numpy or device:
@@ -47,6 +49,8 @@ def infer_volume(image, model, config, body_mask=None, spacing=(4.0, 4.0, 4.0), 
     measure the lesions as resegment.resegment_lesions redraws them on the uptake: the boxes stay
     those of the network's map, and report["lesions"][k]["seed_label"] is the mask_id of the box
     the region grew from."""
+    if resample_order not in (1, 3):
+        raise ValueError("resample_order must be 1 (linear) or 3 (cubic B-spline)")
     if uptake is None and quantify is not None:
         raise ValueError("quantify sets the options of the uptake report: pass uptake too")
     if uptake is None and resegment is not None:
@@ -72,7 +76,10 @@ def infer_volume(image, model, config, body_mask=None, spacing=(4.0, 4.0, 4.0), 
                                        tta_flips=tta_flips)
     expansion = data["bbox_expansion_voxels"]
     if native_shape is not None:
-        prob = resample.resample_volume(prob, native_shape, order=1, output="device")
+        if resample_order == 3:
+            prob = resample.resample_spline(prob, native_shape, clip=(0.0, 1.0), output="device")
+        else:
+            prob = resample.resample_volume(prob, native_shape, order=1, output="device")
         expansion = [int(math.ceil(data["bbox_expansion_mm"] / s)) for s in spacing]
     bboxes = lesion.extract_bboxes(prob, threshold=threshold,
                                    min_volume_cc=data["volume_threshold"]["inference_cc"],

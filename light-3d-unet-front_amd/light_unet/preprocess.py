@@ -307,7 +307,8 @@ def calculate_voxel_thresholds(spacing, volume_cc_list):
     return thresholds
 
 
-def preprocess_volume(image, config, spacing=None, output="numpy", target_spacing=None):
+def preprocess_volume(image, config, spacing=None, output="numpy", target_spacing=None,
+                      resample_order=None):
     """One case of preprocess_case (preprocess_data.py:243-294) without the file I/O:
     (normalized float32 -- what the reference writes to disk --, body mask or None, metadata with
     clip_values, normalization_range, body_mask when enabled and voxel_thresholds when `spacing`
@@ -324,21 +325,33 @@ def preprocess_volume(image, config, spacing=None, output="numpy", target_spacin
     voxel_thresholds then use the grid's real spacing (target_spacing when resampled, else
     spacing).  metadata["resample"] = {"orig_shape", "orig_spacing", "shape", "spacing",
     "applied"}.  The label is the caller's to resample, to the same shape and with order 0:
-    resample_volume(label, metadata["resample"]["shape"], order=0, output="device")."""
+    resample_volume(label, metadata["resample"]["shape"], order=0, output="device").
+    `resample_order` (default None: order 1, and nothing changes) = 3 resamples the image by cubic
+    B-spline interpolation instead (resample.resample_spline), which keeps the peaks of small, hot
+    lesions that order 1 flattens; passing it, 1 included, also records it as
+    metadata["resample"]["order"]."""
     if target_spacing is not None and spacing is None:
         raise ValueError("target_spacing needs the image's spacing")
+    if resample_order not in (None, 1, 3):
+        raise ValueError("resample_order must be 1 (linear) or 3 (cubic B-spline)")
+    if resample_order is not None and target_spacing is None:
+        raise ValueError("resample_order needs target_spacing")
     vol = _volume(image, _device())
     rs_meta = None
     if target_spacing is not None:
         orig_shape = tuple(int(v) for v in vol.shape)
         new_shape = resample.resampled_shape(orig_shape, spacing, target_spacing)
         applied = not np.allclose(spacing, target_spacing, atol=0.1)
-        if applied:
+        if applied and resample_order == 3:
+            vol = resample.resample_spline(vol, new_shape, output="device")
+        elif applied:
             vol = resample.resample_volume(vol, new_shape, order=1, output="device")
         rs_meta = {"orig_shape": list(orig_shape), "orig_spacing": [float(s) for s in spacing],
                    "shape": list(new_shape if applied else orig_shape),
                    "spacing": [float(s) for s in (target_spacing if applied else spacing)],
                    "applied": bool(applied)}
+        if resample_order is not None:
+            rs_meta["order"] = int(resample_order)
         if applied:
             spacing = target_spacing
     inten = config["intensity"]
