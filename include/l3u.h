@@ -43,7 +43,8 @@ typedef unsigned short l3u_bf16;   /* bfloat16 bit pattern (torch.bfloat16 stora
  * removed (round 3); the round-4 entry points.  5: l3u_pw_bwd_chunk (round 6).  Added since
  * without a new version (additive, nothing existing changed): l3u_window_occupancy,
  * l3u_window_blend_masked, l3u_window_gather_flip, l3u_window_tta_merge, l3u_resample,
- * l3u_spline_prefilter, l3u_spline_prefilter_passes, l3u_resample_spline. */
+ * l3u_spline_prefilter, l3u_spline_prefilter_passes, l3u_resample_spline, l3u_gauss_max_radius,
+ * l3u_gauss_axis. */
 #define L3U_ABI_VERSION 5
 int l3u_abi_version(void);
 
@@ -1239,6 +1240,38 @@ int l3u_rs_sweep(const int* items, int n, const int* tiles, int n_tiles, const l
 int l3u_rs_commit(const int* items, int n, const int* tiles, int n_tiles, const long long* aoff,
                   const unsigned long long* arena, int flip, int* own, unsigned long long* reached,
                   int D, int H, int W, hipStream_t stream);
+
+/* ---- Gaussian smoothing (csrc/smooth.hip; light_unet/smooth.py) ----
+ * scipy.ndimage.gaussian_filter(src, sigma, mode = mode, cval = cval) of a [D][H][W] float or
+ * double volume, by this definition (the project's own; its results equal scipy 1.15.3's bit for
+ * bit on tests/golden/smooth.npz).  For each axis a = 0, 1, 2 in that order with sigma[a] > 1e-15
+ * (another axis is skipped, not run with a unit kernel):
+ *  1. Weights, on the host in float64 (numpy): r = (int)(truncate * sigma + 0.5), or a given
+ *     radius; x = -r .. r; phi = exp(-0.5 / (sigma * sigma) * x^2); w = phi / sum(phi), w[0 .. 2r],
+ *     symmetric bit for bit.  The caller uploads w as a device table.
+ *  2. Line pass along a over the current array, every operation in float64 and rounded on its own
+ *     (no product fused with a sum), with v[k] the array along the line and n its length:
+ *         t = v[i] * w[r]
+ *         t = t + (v[i + j] + v[i - j]) * w[j + r]      for j = -r, -r + 1, .., -1 in that order
+ *     (the symmetric branch of scipy's correlate1d, the outermost pair added first); t is rounded
+ *     to the array's type (float or double) and stored; the next axis reads the rounded values.
+ *  3. A tap v[k] outside 0 .. n-1, by mode:
+ *         0 reflect   m = k mod 2n (in 0 .. 2n-1), then 2n - 1 - m where m >= n
+ *         1 mirror    m = k mod (2n - 2), then 2n - 2 - m where m >= n; n == 1 reads voxel 0
+ *         2 nearest   k clamped to 0 .. n-1
+ *         3 constant  the value cval, as a double
+ *     The map is a closed form of k: r may exceed n many times over.
+ * Inputs must be finite.
+ * l3u_gauss_axis: step 2 along `axis` (0, 1 or 2), src -> dst, both of dtype 0 (float) or 1
+ * (double) (l3u_pp_pack's codes); w: DEVICE double[2 * radius + 1] (entries 0 .. radius are read);
+ * 0 <= radius <= l3u_gauss_max_radius() = 64, the halo a workgroup stages.  src and dst must not
+ * overlap: the taps of a line are read after its first outputs are stored.  NULL or overlapping
+ * buffers, another dtype, axis or mode, a radius outside the range and sizes <= 0 return
+ * hipErrorInvalidValue before any launch.  Each output's sum runs in one thread in the stated
+ * order: no atomics, and the result does not depend on the launch shape. */
+int l3u_gauss_max_radius(void);
+int l3u_gauss_axis(const void* src, void* dst, int dtype, int D, int H, int W, int axis,
+                   const double* w, int radius, int mode, double cval, hipStream_t stream);
 
 #ifdef __cplusplus
 }

@@ -176,6 +176,9 @@ _SIGS = {
     "l3u_rs_grow": [P, P, P, I, P, P, I, I, P, P, P, P, I, P, P, I, I, I, I, P],
     "l3u_rs_sweep": [P, I, P, I, P, P, I, P, I, I, I, P],
     "l3u_rs_commit": [P, I, P, I, P, P, I, P, P, I, I, I, P],
+    # Gaussian smoothing, one axis per call: (src, dst, dtype, D, H, W, axis, w, radius, mode, cval)
+    "l3u_gauss_max_radius": [],
+    "l3u_gauss_axis": [P, P, I, I, I, I, I, P, I, I, D, P],
 }
 # entry points with a _bf16 twin (same arguments; saved activations stored as bf16, gradients
 # fp32, include/l3u.h)
@@ -201,7 +204,7 @@ _QUERIES = {"l3u_abi_version", "l3u_dw3_nchunk", "l3u_pw_stat_nsb", "l3u_pw_bwd_
             "l3u_dw3_bwd_rank1", "l3u_pw_bwd2_supported", "l3u_pw_bwd_chunk",
             "l3u_ccl_lv_max_levels", "l3u_pp_select_ws_bytes", "l3u_pp_morph_max_iters",
             "l3u_loc_nblocks", "l3u_surf_nblocks", "l3u_qt_corner_blocks", "l3u_qt_pair_parts",
-            "l3u_rs_path", "l3u_rs_tiles"}
+            "l3u_rs_path", "l3u_rs_tiles", "l3u_gauss_max_radius"}
 
 LOC_BLOCK = 4096    # L3U_LOC_BLOCK
 

@@ -13,12 +13,13 @@ from . import lesion
 from . import quantify as _quantify
 from . import resample
 from . import resegment as _resegment
+from . import smooth as _smooth
 from .utils import sliding_window_inference_3d
 
 
 def infer_volume(image, model, config, body_mask=None, spacing=(4.0, 4.0, 4.0), threshold=None,
                  forward_cache=None, tta_flips=None, native_shape=None, uptake=None, quantify=None,
-                 resegment=None, resample_order=1):
+                 resegment=None, resample_order=1, smooth_fwhm_mm=None):
     """(prob_map, bboxes) of one case: prob_map the float32 numpy [D, H, W] map the reference
     saves (times `body_mask` when config["data"]["body_mask"] has both `enabled` and
     `apply_to_inference`, inferencer.py:136-137, :161-162; otherwise the mask is ignored), bboxes
@@ -48,16 +49,22 @@ def infer_volume(image, model, config, body_mask=None, spacing=(4.0, 4.0, 4.0), 
     ..., "grow_mm": ...} (resegment.check_resegment; default None: nothing changes) has the report
     measure the lesions as resegment.resegment_lesions redraws them on the uptake: the boxes stay
     those of the network's map, and report["lesions"][k]["seed_label"] is the mask_id of the box
-    the region grew from."""
+    the region grew from.  `smooth_fwhm_mm` (default None: nothing changes) is passed through to
+    quantify.lesion_uptake: the report is that of the uptake after a Gaussian post-filter of that
+    FWHM in mm, and gains "smooth"; the map and the boxes do not depend on it."""
     if resample_order not in (1, 3):
         raise ValueError("resample_order must be 1 (linear) or 3 (cubic B-spline)")
     if uptake is None and quantify is not None:
         raise ValueError("quantify sets the options of the uptake report: pass uptake too")
     if uptake is None and resegment is not None:
         raise ValueError("resegment redraws the lesions on the uptake: pass uptake too")
+    if uptake is None and smooth_fwhm_mm is not None:
+        raise ValueError("smooth_fwhm_mm filters the uptake: pass uptake too")
     if uptake is not None:
         peak_ml, want_dmax = _quantify.check_config(quantify)
         _resegment.check_resegment(resegment)
+        if smooth_fwhm_mm is not None:
+            _smooth.smooth_record(smooth_fwhm_mm, _quantify._spacing3(spacing))
         want = tuple(int(v) for v in (native_shape if native_shape is not None else image.shape[-3:]))
         if tuple(int(v) for v in uptake.shape) != want:
             raise ValueError(f"uptake must be on the grid the map ends on, {want}; got "
@@ -89,5 +96,5 @@ def infer_volume(image, model, config, body_mask=None, spacing=(4.0, 4.0, 4.0), 
     report = _quantify.lesion_uptake(
         uptake, prob, spacing=spacing, threshold=threshold, peak_ml=peak_ml, dmax=want_dmax,
         min_size=lesion.min_voxels_for(data["volume_threshold"]["inference_cc"], spacing),
-        resegment=resegment)
+        resegment=resegment, smooth_fwhm_mm=smooth_fwhm_mm)
     return prob.cpu().numpy(), bboxes, report

@@ -36,6 +36,7 @@ import torch
 from . import _native as nat
 from . import lesion
 from . import preprocess as pp
+from . import smooth as _smooth
 
 MAX_RADIUS_VOXELS = 4     # csrc/quantify.hip kMaxR: the halo the sphere mean stages
 MAX_CANDIDATES = 1 << 18  # csrc/quantify.hip kMaxCand
@@ -203,6 +204,7 @@ def _zyx(flat, shape):
 
 
 # ------------------------------------------------------------------ the public entry point
+@_smooth.takes_smooth_fwhm
 def lesion_uptake(uptake, mask, spacing=(4.0, 4.0, 4.0), threshold=0.5, min_size=0, peak_ml=1.0,
                   dmax=True, resegment=None):
     """The uptake report of one case.
@@ -227,7 +229,15 @@ def lesion_uptake(uptake, mask, spacing=(4.0, 4.0, 4.0), threshold=0.5, min_size
     resegment.resegment_lesions redraws them on the uptake, seeded by the lesions above: the report
     is that of its regions, every lesion row gains "seed_label", "seed_voxels" and "threshold", and
     the report "resegment": {"method", "value", "grow_mm", "below_threshold", "absorbed"}, the two
-    lists holding the labels of the seeds that left no region."""
+    lists holding the labels of the seeds that left no region.
+
+    Keyword only, added by smooth.takes_smooth_fwhm: smooth_fwhm_mm (default None: nothing
+    changes) = the FWHM in mm, a scalar or one value per axis, of a Gaussian post-filter
+    (smooth.smooth_fwhm, mode "reflect") applied once, on the device, to the float32 uptake before
+    anything reads it: the peak, the reductions and the resegmentation with its relative
+    thresholds all see the filtered volume, and the report gains "smooth": {"fwhm_mm",
+    "sigma_voxels", "radius"}, one value per axis.  The mask, the seeds and the caller's uptake
+    are untouched."""
     sp = _spacing3(spacing)
     peak_ml = _peak_ml(peak_ml)
     rs_cfg = None

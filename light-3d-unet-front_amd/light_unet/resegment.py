@@ -40,6 +40,7 @@ import torch
 from . import _native as nat
 from . import lesion
 from . import quantify as _qt
+from . import smooth as _smooth
 from .utils import _checked_body_mask
 
 METHODS = ("fixed", "relative")
@@ -130,12 +131,15 @@ class Resegmented:
     labels 1..m, stats as l3u_ccl_stats_b writes them); seed_label int32 [m]: the seed of each
     region; per seed (n of them): status int8 (0 kept, 1 below threshold, 2 absorbed), thresholds
     float64, seed_voxels and reached int64; path int8 (0 LDS, 1 tiled) and sweeps int32 (the
-    sweeps, or for tiled seeds the launches, that changed a word) say how the device got there."""
+    sweeps, or for tiled seeds the launches, that changed a word) say how the device got there.
+    smooth: None, or {"fwhm_mm", "sigma_voxels", "radius"} of the post-filter the uptake went
+    through first (resegment_lesions' smooth_fwhm_mm)."""
 
     def __init__(self, components, seed_label, status, thresholds, seed_voxels, reached, path, sweeps):
         self.components, self.seed_label, self.status = components, seed_label, status
         self.thresholds, self.seed_voxels, self.reached = thresholds, seed_voxels, reached
         self.path, self.sweeps = path, sweeps
+        self.smooth = None
 
 
 def _empty(labels):
@@ -221,6 +225,7 @@ def _stats(lab, remap, num, shape):
 
 
 # ------------------------------------------------------------------ the public entry point
+@_smooth.takes_smooth_fwhm
 def resegment_lesions(uptake, mask, spacing=(4.0, 4.0, 4.0), method="fixed", value=4.0, grow_mm=None,
                       threshold=0.5, min_size=0, body_mask=None, max_lds_bytes=0):
     """The seeds of `mask` resegmented on `uptake`, as the module docstring defines it.
@@ -235,6 +240,11 @@ def resegment_lesions(uptake, mask, spacing=(4.0, 4.0, 4.0), method="fixed", val
     int16, float32); voxels where it is 0 are no candidates.
     max_lds_bytes: the LDS a seed's two box bitmaps may take before the seed goes the tiled way
     (0: the default and the most, 64 KiB); the result does not depend on it.
+    Keyword only, added by smooth.takes_smooth_fwhm: smooth_fwhm_mm (default None: nothing
+    changes), the FWHM in mm, a scalar or one value per axis, of a Gaussian post-filter
+    (smooth.smooth_fwhm, mode "reflect") applied once, on the device, to the float32 uptake: the
+    seed maxima, the thresholds and the growing read the filtered volume; the seeds and the
+    caller's uptake are untouched, and the result's `smooth` says what ran.
 
     Returns a Resegmented.  With no seeds everything is empty and the label map is zeros."""
     sp = _qt._spacing3(spacing)
